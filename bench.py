@@ -1,8 +1,15 @@
 """Benchmark of the MI355X path-tracing kernel on BASELINE.json's headline config.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cornell]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cornell] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K frames and prints the result line.  `--full` adds the
+records that take runs of their own: the FP32 fast path (`f32_fast_path`), the CPU baseline
+(`cpu_baseline`) and the C-ABI device list (`abi_device_list`), described below.
+`--dump-outputs DIR` writes the frame of the last timed step — the (height, width, 3) linear
+radiance image a caller of the timed path receives, in the line's dtype — as DIR/frame.npy; the
+scene, camera and seed are fixed by the config, so two builds can be compared pixel for pixel.
 
 One step = one full frame of the config (Cornell box 600x600, 200 spp, depth 50, redirect
 target, seed 234 — test/Main.hs:188-218) with the scene already resident in HBM.  With N
@@ -24,11 +31,12 @@ workgroups fill the rest instead of waiting (Cornell +4 % at 1 GPU, +26 % on one
 an 8-GPU frame).
 
 Precision: the line is measured with the binary64 kernel (`dtype` "f64"), the reference's
-arithmetic (`V3 Double`, Core.hs:29-31); the FP32 fast path is measured right after it on the
-same frames and reported beside it as `f32_fast_path` (a labelled second record, not `value`).
+arithmetic (`V3 Double`, Core.hs:29-31); with `--full` the FP32 fast path is measured right after
+it on the same frames and reported beside it as `f32_fast_path` (a labelled second record, not
+`value`).
 
-Extra fields: `roofline` — the physical ceiling of the render kernel: VALU instruction issue
-(the kernel's PMC-counted VALU wave-instructions per launch, profiles/pmc_valu.json, scaled to the
+Extra fields (`cpu_baseline` and `abi_device_list` with `--full` only): `roofline` — the
+physical ceiling of the render kernel: VALU instruction issue (the kernel's PMC-counted VALU wave-instructions per launch, profiles/pmc_valu.json, scaled to the
 samples this launch renders, / its device time per frame from HIP events over the timed region —
 `kernel_ms`, the span of the timed frames / frames; `launch_ms` is the average single-launch
 duration, longer when two launches overlap — against 256 CUs x 4 SIMDs x one wave64 VALU
@@ -302,10 +310,18 @@ def main():
     ap.add_argument("--config", default="cornell", choices=["cornell", "readme", "demo1", "demo1_1200x800", "bunny_cornell", "pawn_fog"])
     ap.add_argument("--row-block", type=int, default=1,
                     help="rows are dealt to ranks in blocks of this many (1: 600 rows split exactly 8 ways)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the FP32 fast-path record, the "
+                         "CPU baseline and the C-ABI device-list record (see --no-f32, --no-cpu-baseline, "
+                         "--no-abi-devices to drop one of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame of the last timed step (height x width x 3, "
+                         "the line's dtype) as DIR/frame.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline record")
     ap.add_argument("--precision", default="f64", choices=["f64", "f32"],
                     help="the kernel precision of the line's value (f64: the reference's binary64)")
-    ap.add_argument("--no-f32", action="store_true", help="skip the FP32 fast-path record after an f64 line")
+    ap.add_argument("--no-f32", action="store_true",
+                    help="with --full: skip the FP32 fast-path record after an f64 line")
     ap.add_argument("--plan", default="auto", choices=["auto", "overlapped", "solo"],
                     help="work plan of each render (rt_exec RT_EXEC_SOLO): auto = solo with one stream, "
                          "overlapped otherwise; tools/pmc_run.sh counts one-stream launches of the "
@@ -319,7 +335,7 @@ def main():
     ap.add_argument("--sim-shards", type=int, default=1,
                     help="diagnostic, one process: render only shard 0 of N (one rank's share of an N-GPU frame)")
     ap.add_argument("--no-abi-devices", action="store_true",
-                    help="skip the abi_device_list record (rank 0, after the ranks' measurement)")
+                    help="with --full: skip the abi_device_list record (rank 0, after the ranks' measurement)")
     ap.add_argument("--abi-helper", action="store_true",
                     help="internal: the process that times the C-ABI device list for rank 0 (started "
                          "before rank 0 touches a GPU; waits for 'go <devices>' on stdin)")
@@ -332,6 +348,10 @@ def main():
         return abi_helper(args)
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if not args.full:  # a plain run measures the headline figure only
+        args.no_f32 = args.no_cpu_baseline = args.no_abi_devices = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no external launcher: start one rank per GPU ourselves (before anything touches a GPU)
         raise SystemExit(spawn_ranks(args.gpus))
@@ -503,7 +523,7 @@ def main():
         if ev:
             span = max(ev[0][0].elapsed_time(b) for _, b in ev[-len(streams):])
             kernel_ms = span / len(ev)
-        check = None
+        check = img = None
         if rank == 0:  # (the frame exists on rank 0 only)
             import numpy as np
             last = (frame[0] - 1) % nbuf
@@ -536,10 +556,16 @@ def main():
                              "a frame's render end -> its RCCL gather to rank 0 done on this rank (probe stream, RCCL only); "
                              "ms_per_step_local: the rank's own timed region / frames before the max over ranks"}
         return dict(elapsed=elapsed, launch_ms=launch_ms, kernel_ms=kernel_ms, warm_frames=warm_frames,
-                    warm_s=warm_s, check=check, streams=len(streams), ranks=ranks)
+                    warm_s=warm_s, check=check, streams=len(streams), ranks=ranks,
+                    frame=img if args.dump_outputs else None)
 
     precisions = [args.precision] + (["f32"] if args.precision == "f64" and not args.no_f32 else [])
     res = {p: measure(p) for p in precisions}
+    if args.dump_outputs and rank == 0:
+        # the last timed frame of the line's own precision, as the caller of the timed path gets it
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "frame.npy"), np.ascontiguousarray(res[precisions[0]]["frame"]))
 
     total_samples = h * w * spp
     real_rows = int((shard_row_index(h, n_sh, sh, args.row_block) < h).sum())

@@ -40,10 +40,10 @@ for s in $STEPS; do
       timeout -k 10 900 python -u -m pytest tests -x -v -m gpu --timeout 300 --timeout-method thread ${PYTEST_K:+-k "$PYTEST_K"} > "$OUT/pytest_gpu.log" 2>&1 || { echo "pytest failed"; grep -E "FAILED|Error" "$OUT/pytest_gpu.log" | head -20; exit 1; }
       tail -1 "$OUT/pytest_gpu.log" ;;
     bench)
-      timeout -k 10 300 python bench.py --steps 20 --warmup 5 > "$OUT/bench_cornell.json" 2> "$OUT/bench_cornell.err" || { echo "bench failed"; tail -5 "$OUT/bench_cornell.err"; exit 1; } ;;
+      timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_cornell.json" 2> "$OUT/bench_cornell.err" || { echo "bench failed"; tail -5 "$OUT/bench_cornell.err"; exit 1; } ;;
     benchall)
       for c in ${CONFIGS:-$ALL_CONFIGS}; do
-        timeout -k 10 300 python bench.py --config $c --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench_$c.json" 2>> "$OUT/bench_other.err" || { echo "bench $c failed"; exit 1; }
+        timeout -k 10 300 python bench.py --full --config $c --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench_$c.json" 2>> "$OUT/bench_other.err" || { echo "bench $c failed"; exit 1; }
       done ;;
     summary)
       for f in "$OUT"/bench_*.json; do python3 - "$f" <<'PY'

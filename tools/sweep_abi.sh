@@ -8,7 +8,7 @@ for rep in 1 2; do
 for set in $SETS; do
   envs=""; [ "$set" != base ] && envs=$(echo $set | tr ',' ' ')
   f=$OUT/${CFG}_${PREC}_$(echo $set | tr ',=' '_-')_r$rep.json
-  env $envs timeout -k 10 300 python bench.py --no-cpu-baseline --no-f32 --precision $PREC --config $CFG --steps $STEPS \
+  env $envs timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-f32 --precision $PREC --config $CFG --steps $STEPS \
     --warmup-s 0.3 > $f 2>>$OUT/err.log || { echo "fail $set"; exit 1; }
   python3 -c "
 import json;d=json.loads(open('$f').read().strip().splitlines()[-1]);a=d.get('abi_device_list') or {}
