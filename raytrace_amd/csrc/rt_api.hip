@@ -20,6 +20,7 @@
 
 #include "../../include/rt.h"
 #include "rt_internal.h"
+#include "rt_kernel_class.h"
 
 namespace {
 
@@ -178,12 +179,12 @@ int ensure_precision(const rt_device_scene* s) {
     // stacks in the workgroup's share of the CU's 160 KB LDS at the kernel's occupancy (1 KB
     // granules; 4 x waves-per-SIMD waves per CU, `block` threads per workgroup); env
     // RT_AMD_LDS_NODES caps it (0 disables, for experiments)
-    const int waves = std::max(1, rt_render_waves((const KernelParamsT<R>*)nullptr, s->variant));
-    const int block = rt_render_block((const KernelParamsT<R>*)nullptr, s->variant);
+    const KernelClass c = rt_class_of(sizeof(R) == 8, s->variant);
+    const int waves = std::max(1, rt_class_waves(sizeof(R) == 8, c));
+    const int block = rt_class_block(sizeof(R) == 8, c);
     const int per_cu = std::max(1, 4 * waves * 64 / block);
     const int budget = (163840 / per_cu / 1024) * 1024 - 1024;
-    const int used = rt_render_acc_lds((const KernelParamsT<R>*)nullptr, s->variant) +
-                     (s->stack_depth + 1) * block * (int)sizeof(int);
+    const int used = (int)rt_class_lds_bytes(sizeof(R) == 8, c, s->stack_depth, 0);
     A.lds_nodes = std::max(0, std::min(s->host->surface_nodes, (budget - used) / 64));
     if (const char* e = rt_knob("RT_AMD_LDS_NODES")) A.lds_nodes = std::min(A.lds_nodes, std::max(0, atoi(e)));
   }
@@ -254,8 +255,8 @@ int render_async(const rt_device_scene* s, const rt_camera_settings* cs, uint64_
   P.stack_depth = s->stack_depth;
   P.lds_nodes = A.lds_nodes;
   P.n_prims = s->n_prims;
-  rt_host_plan_work(P, (long long)A.resident_blocks * rt_render_block((const KernelParamsT<R>*)nullptr, s->variant),
-                    (s->variant & RT_VAR_BASE) == RT_VAR_FLAT, lone);
+  const KernelClass c = rt_class_of(sizeof(R) == 8, s->variant);
+  rt_host_plan_work(P, (long long)A.resident_blocks * rt_class_block(sizeof(R) == 8, c), c.var == RT_VAR_FLAT, lone);
   P.trav_exit_pct = sizeof(R) == 8 ? s->trav_exit_pct64 : s->trav_exit_pct;
   P.out_frame_rows = frame_rows;
   HIP_TRY(hipSetDevice(s->device));
@@ -540,8 +541,7 @@ int render_one(rt_multi_scene* M, const rt_camera_settings* cs, uint64_t seed, c
     stats->bvh_nodes = s->n_nodes;
     stats->max_stack = s->max_depth;
     stats->device_allocs = allocs;
-    stats->kernel_block = f32 ? rt_render_block((const KernelParamsT<float>*)nullptr, s->variant)
-                              : rt_render_block((const KernelParamsT<double>*)nullptr, s->variant);
+    stats->kernel_block = rt_class_block(!f32, rt_class_of(!f32, s->variant));
     stats->total_ms = build_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   return RT_OK;
@@ -703,8 +703,7 @@ int multi_render(rt_multi_scene* M, const rt_camera_settings* cs, uint64_t seed,
     stats->bvh_nodes = M->scenes[0]->n_nodes;
     stats->max_stack = M->scenes[0]->max_depth;
     stats->device_allocs = allocs;
-    stats->kernel_block = f32 ? rt_render_block((const KernelParamsT<float>*)nullptr, M->scenes[0]->variant)
-                              : rt_render_block((const KernelParamsT<double>*)nullptr, M->scenes[0]->variant);
+    stats->kernel_block = rt_class_block(!f32, rt_class_of(!f32, M->scenes[0]->variant));
     stats->total_ms = build_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   return rc;

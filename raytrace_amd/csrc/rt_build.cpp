@@ -17,6 +17,7 @@
 #include "rt_bvh.h"
 #include "rt_encode8_table.h"
 #include "rt_internal.h"
+#include "rt_kernel_class.h"
 
 const char* rt_knob(const char* name) {
   const char* on = std::getenv("RT_AMD_EXPERIMENTS");
@@ -883,7 +884,7 @@ int rt_host_build_scene(const rt_scene* sc, HostScene& S, std::string& err) {
 int rt_host_variant(bool flat, int n_media, bool noise, bool mats, bool tex, bool inst, int leaf_kind, bool media_late,
                     int stack_depth) {
   int v = flat ? RT_VAR_FLAT : RT_VAR_BVH;
-  // the BVH kernels' 1024-lane classes (rt_render_kernel.h RT_BLOCK_BVH_OF) hold RT_WIDE_STACK_ROWS
+  // the BVH kernels' 1024-lane classes (rt_kernel_class.h rt_class_block_wide) hold RT_WIDE_STACK_ROWS
   // stack rows per lane; a deeper BVH takes the 512-lane twin of its class
   const int narrow = !flat && stack_depth + 1 > RT_WIDE_STACK_ROWS ? RT_VAR_NARROW : 0;
   // media events in the shading phase; env RT_AMD_MEDIA_LATE=0 keeps them in the traversal loop's
@@ -1103,9 +1104,9 @@ void rt_host_plan_work(KernelParamsT<R>& P, long long resident_lanes, bool two_s
   P.n_items = (int)items;
   // commit aggregation: a phase qualifies when a pool of RT_POOL consecutive ids spans at most a
   // slot's pixels (rt_render_kernel.h WaveWork); env RT_AMD_AGG=0 turns it off (A/B, same LDS)
-  const int slot_pix = !two_sizes                          ? RT_AGG_PIX_BVH
-                       : sizeof(R) == 8 || P.n_media == 0 ? RT_AGG_PIX_FLAT_F64  // (rt_render_kernel.h RT_AGG_WIDE_OF)
-                                                          : RT_AGG_PIX_FLAT;
+  // (the slot width depends on the class's base and media only: rt_kernel_class.h rt_class_agg_pix)
+  const KernelClass c{two_sizes ? RT_VAR_FLAT : RT_VAR_BVH, 0, P.n_media > 0 ? 1 : 0, false, false, 0, false};
+  const int slot_pix = rt_class_agg_pix(sizeof(R) == 8, c);
   const int pool = 1 << P.pool_shift;
   auto spans = [&](int n) { return n > 0 && (pool - 1 + n - 1) / n + 1 <= slot_pix; };
   bool agg = tile_pixels < (1ll << 24);  // the item's aggregation code shares its tile-pixel word

@@ -32,7 +32,7 @@
 #define RT_BLOCK 64
 #endif
 #ifndef RT_BLOCK_BVH
-#define RT_BLOCK_BVH 256      // BVH kernel workgroup at 5 waves/SIMD (others: rt_render_kernel.h RT_BLOCK_OF)
+#define RT_BLOCK_BVH 256      // BVH kernel workgroup at 5 waves/SIMD (others: rt_kernel_class.h rt_class_block)
 #endif
 // BVH nodes of a scene at most: the FP32 kernels address a node as a 32-bit byte offset
 // node * 64 from the nodes' base (rt_trace.h RT_NODE_SADDR)
@@ -134,7 +134,8 @@
 #define RT_VAR_MEDIA_LATE 512  // flag (with RT_VAR_MEDIA, RT_VAR_BVH): the media events in the shading phase
 #define RT_VAR_NARROW 1024     // flag: a 1024-lane kernel class launches its 512-lane twin (a deep BVH's stacks)
 // The deepest stack (rows) one 1024-lane workgroup holds beside its lanes' item sums and slots
-// (binary64: 48 + 16 B per lane; the FP32 classes take the same rule): deeper BVHs run RT_VAR_NARROW
+// (binary64: 48 + 16 B per lane; the FP32 classes take the same rule; rt_kernel_class.h checks
+// it against the classes' LDS at compile time): deeper BVHs run RT_VAR_NARROW
 #define RT_WIDE_STACK_ROWS 23
 // Experiment knobs (rt_build.cpp): the library reads its RT_AMD_* tuning variables (variant,
 // chunking, aggregation, prefix, box groups, LDS staging, ...) only when RT_AMD_EXPERIMENTS is set
@@ -434,12 +435,6 @@ void rt_host_encode8_thresholds(int encoding, double* thr);
 // resident workgroups of the render kernel for a given LDS stack depth (occupancy query)
 int rt_render_resident_blocks(const KernelParams*, int device, int stack_depth, int variant, int lds_nodes);
 int rt_render_resident_blocks(const KernelParams64*, int device, int stack_depth, int variant, int lds_nodes);
-int rt_render_waves(const KernelParams*, int variant);
-int rt_render_waves(const KernelParams64*, int variant);
-int rt_render_block(const KernelParams*, int variant);  // the workgroup size of a variant's kernel
-int rt_render_block(const KernelParams64*, int variant);
-int rt_render_acc_lds(const KernelParams*, int variant);
-int rt_render_acc_lds(const KernelParams64*, int variant);
 int rt_launch_render(const KernelParams& p, int grid_blocks, int variant, void* stream);
 int rt_launch_render(const KernelParams64& p, int grid_blocks, int variant, void* stream);
 // accum / nanflag -> out (mean over spp, NaN where flagged)

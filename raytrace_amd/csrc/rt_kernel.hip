@@ -6,7 +6,7 @@
 // rt_render_kernel: a grid of exactly the resident workgroups (occupancy query), instantiated per
 // scene class (texture level, media, materials, leaf class, instancing; see render_kernel_of).
 // Workgroups: one wave (64 lanes) for the flat kernels; 768 or 1024 lanes for the BVH classes at
-// 3 / 6 or 4 / 8 waves per SIMD, 256 otherwise (rt_render_kernel.h RT_BLOCK_OF; 512-lane twins for
+// 3 / 6 or 4 / 8 waves per SIMD, 256 otherwise (rt_kernel_class.h rt_class_block; 512-lane twins for
 // deep BVHs).  Waves start with a static pool of item ids and refill it with one returning
 // atomicAdd on one of four queue heads (ballot the lanes that need work; ids are handed out in
 // lane order); ids are

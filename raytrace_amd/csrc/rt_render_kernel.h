@@ -7,18 +7,8 @@
 
 #include <type_traits>
 
+#include "rt_kernel_class.h"
 #include "rt_trace.h"
-
-// Where the lanes' item sums live (rt_trace.h Acc / AccLds).  Same-box A/B against registers
-// (profiles/r3/slim): in LDS they free the VGPRs that let the FP32 BVH kernel without media run 6
-// waves per SIMD (bunny-Cornell 107.2 -> 100.6 ms) and trim the binary64 BVH kernels (bunny 162.7
-// -> 157.6, pawn+fog 643 -> 631); the flat kernels, which read their scene with scalar loads that
-// share the LDS return counter, lose 2-3.5 % (Cornell f64 6.12 -> 6.33) and the FP32 media kernel
-// 2.8 %, so those keep registers.  -DRT_ACC_IN_LDS=0 keeps registers everywhere.
-#ifndef RT_ACC_IN_LDS
-#define RT_ACC_IN_LDS 1
-#endif
-#define RT_ACC_LDS_OF(kVar, kMedia) (RT_ACC_IN_LDS && (kVar) != RT_VAR_FLAT && (RT_F64 || !(kMedia)))
 
 namespace RT_NS {
 
@@ -74,15 +64,9 @@ static_assert((RT_QUEUES & (RT_QUEUES - 1)) == 0 && RT_QUEUES <= 8, "RT_QUEUES: 
 // sums: the image is bit-identical either way.
 // (keeping the item's pixel offset within the slot in its code, resolved at the item's start
 // instead of one LDS read at its commit, measured no faster: Cornell f64 5.77 vs 5.74 ms)
-static_assert(RT_AGG_SLOTS_FLAT < 255 && RT_AGG_SLOTS_FLAT_F64 < 255 && RT_AGG_SLOTS_BVH < 255,
-              "slot + 1 must fit the 8 bits of rt_trace.h ItemCtx::tp");
-
-// LDS of the aggregation slots per wave: kSlots x kPix x RT_ACC_WORDS words + 2 kSlots header ints
+// the 64-bit words of one aggregation slot (rt_kernel_class.h rt_class_agg_bytes: its LDS per wave)
 template <int kSlots, int kPix>
-struct AggGeom {
-  static constexpr int kWords = kPix * RT_ACC_WORDS(real);  // 64-bit words per slot
-  static constexpr int kWaveBytes = kSlots * kWords * 8 + 2 * kSlots * 4;
-};
+struct AggGeom { static constexpr int kWords = kPix * RT_ACC_WORDS(real); };
 
 // The work queue of the flat kernels re-reads its kernel-argument fields at each use; the BVH
 // kernels' does in FP32 only (binary64 demo1 / pawn+fog -0.7 % with them held, Cornell's flat
@@ -305,172 +289,25 @@ struct WaveWork {
 
 }  // namespace
 
-// Variants (rt_internal.h RT_VAR_*), chosen per scene by the host:
-//  RT_VAR_FLAT: every primitive set is one flat leaf; no LDS: the records are read with
-//    wave-uniform addresses (scalar loads into SGPRs, scalar-cache resident); lockstep loop.
-//  RT_VAR_BVH / RT_VAR_BVH_LOCKSTEP: BVH scenes; dynamic LDS = the lanes' traversal stacks
-//    [depth][lane] followed by the top P.lds_nodes nodes.  The default decouples traversal
-//    from shading per lane (rt_trace.h lane_loop_bvh); the lockstep loop runs every query of a
-//    segment with the whole wave (kept for experiments; images are bit-identical).
-// Register budget: occupancy floor (waves per SIMD), per kernel class and precision — the table
-// below (RT_WAVES_OF), each entry measured against its neighbours (DESIGN_HISTORY §1a,
-// §4).  Since round 6 every entry also keeps its class free of VGPR spills (tools/spill_gate.py
-// fails the build otherwise): the binary64 full-material BVH classes, the binary64 instanced
-// full-material class, the FP32 full-material generic-leaf class and the FP32 instanced media-chain
-// classes each run one wave less than their round-5 entries.
-#ifndef RT_WAVES_FLAT
-#define RT_WAVES_FLAT 7
-#endif
-#ifndef RT_WAVES_FLAT_NOISE
-#define RT_WAVES_FLAT_NOISE 5
-#endif
-#ifndef RT_WAVES_BVH
-#define RT_WAVES_BVH 5
-#endif
-// knobs for the lightest instantiations (constant textures; BVH: no media).  The flat kernel with
-// constant textures runs 8 waves since round 4: with the kernel arguments re-read per iteration
-// (rt_trace.h RT_KARGS) and shade's unconditional ray update it needs 64 VGPRs without spills
-// (Cornell FP32 3.162 -> 3.075 ms against 7 waves, profiles/r4/unc_ab); round 3's 8-wave build
-// spilled 6 VGPRs and gained nothing
-#ifndef RT_WAVES_FLAT_TEX0
-#define RT_WAVES_FLAT_TEX0 8
-#endif
-#ifndef RT_WAVES_BVH_LITE
-#define RT_WAVES_BVH_LITE 6  // 80 VGPRs once the item sums moved to LDS: bunny-Cornell 107.2 -> 100.6 ms at 6 (profiles/r3/slim)
-#endif
-// binary64: every real is a register pair, so the same code needs about twice the VGPRs; the
-// lightest instantiations (constant textures, no media, no materials beyond the diffuse ones)
-// keep more waves
-#ifndef RT_WAVES64_FLAT_LITE
-#define RT_WAVES64_FLAT_LITE 5  // 96 VGPRs, no spills (round 4): Cornell binary64 5.442 -> 5.315 ms against 4
-#endif
-#ifndef RT_WAVES64_FLAT
-#define RT_WAVES64_FLAT 4  // 100 VGPRs without MachineLICM (round 4: 2, with it 195 VGPRs; readme 0.65 -> 0.46 ms)
-#endif
-#ifndef RT_WAVES64_BVH_LITE
-#define RT_WAVES64_BVH_LITE 4  // 163 ms bunny-Cornell vs 180 at 3 once the BVH nodes were tested in FP32 (profiles/r2/waves64)
-#endif
-#ifndef RT_WAVES64_BVH
-#define RT_WAVES64_BVH 4  // demo1 69.9 ms vs 76.6 at 3 (profiles/r2/waves64); textured scenes, instances
-#endif
-#ifndef RT_WAVES64_BVH_MATS
-// constant textures, the full material set (demo1).  Round 5 ran it at 5 (57.0 -> 56.4 ms), where
-// every leaf class of it spilled 4-14 VGPRs; round 6 keeps every dispatchable kernel spill-free
-// (tools/spill_gate.py), so 4
-#define RT_WAVES64_BVH_MATS 4
-#endif
-#ifndef RT_WAVES64_BVH_MEDIA
-#define RT_WAVES64_BVH_MEDIA 3  // the media chain kernels (pawn+fog 641 ms at 3, 883 at 4), instanced with textures / media
-#endif
-#ifndef RT_WAVES64_BVH_INST_MATS
-#define RT_WAVES64_BVH_INST_MATS 3  // instances with the full material set: 1 VGPR spilled at 4
-#endif
-#ifndef RT_WAVES64_BVH_MEDIA_LATE
-#define RT_WAVES64_BVH_MEDIA_LATE 4  // media events in the shading phase (kMedia 2): pawn+fog 508 -> 476 ms
-#endif
-#ifndef RT_WAVES_BVH_MEDIA_LATE
-// FP32 pawn+fog: 310.7 -> 302 ms at 7 against 5 (profiles/r5/licm); 6, in two 768-lane workgroups
-// per CU, stages 520 of its 631 surface nodes per copy against 120 at 7: 302.7 -> 276.1 ms (4:
-// 318, 8: 297; profiles/r5/occ)
-#define RT_WAVES_BVH_MEDIA_LATE 6
-#endif
-#ifndef RT_WAVES_BVH_MATS
-#define RT_WAVES_BVH_MATS 8  // FP32 BVH, constant textures, the full material set, no media (demo1 39.7 -> 39.25 ms)
-#endif
-#ifndef RT_WAVES_BVH_MATS_GENERIC
-#define RT_WAVES_BVH_MATS_GENERIC 7  // ... with generic leaves: 4 VGPRs spilled at 8
-#endif
-#ifndef RT_WAVES_BVH_INST_CHAIN
-#define RT_WAVES_BVH_INST_CHAIN 4  // FP32 instances with the media query chain: 2-25 VGPRs spilled at 5
-#endif
-// kLeaf: the leaf class of the instantiation (0 generic, 1 triangles, 2 spheres; rt_trace.h trav_round)
-#if RT_F64
-#define RT_WAVES_OF(kVar, kTex, kMedia, kMats, kInst, kLeaf)                                        \
-  ((kVar) == RT_VAR_FLAT ? ((kTex) == 0 && !(kMedia) && !(kMats) ? RT_WAVES64_FLAT_LITE : RT_WAVES64_FLAT) \
-                         : (kInst) && ((kTex) != 0 || (kMedia) != 0) ? RT_WAVES64_BVH_MEDIA          \
-                         : (kInst) && (kMats) ? RT_WAVES64_BVH_INST_MATS                            \
-                         : (kMedia) == 2 ? RT_WAVES64_BVH_MEDIA_LATE                                \
-                         : (kMedia) ? RT_WAVES64_BVH_MEDIA                                          \
-                         : (kTex) == 0 && !(kMats) ? RT_WAVES64_BVH_LITE                            \
-                         : (kTex) == 0 && !(kInst) ? RT_WAVES64_BVH_MATS : RT_WAVES64_BVH)
-#else
-#define RT_WAVES_OF(kVar, kTex, kMedia, kMats, kInst, kLeaf)                                              \
-  ((kVar) == RT_VAR_FLAT ? ((kTex) == 2 ? RT_WAVES_FLAT_NOISE : (kTex) == 0 ? RT_WAVES_FLAT_TEX0 : RT_WAVES_FLAT) \
-                         : (kMedia) == 2 ? ((kInst) ? RT_WAVES_BVH : RT_WAVES_BVH_MEDIA_LATE)             \
-                         : (kMedia) == 1 && (kInst) ? RT_WAVES_BVH_INST_CHAIN                             \
-                         : (kTex) == 0 && !(kMedia) && (kMats) && !(kInst)                                \
-                             ? ((kLeaf) == 0 ? RT_WAVES_BVH_MATS_GENERIC : RT_WAVES_BVH_MATS)               \
-                         : ((kTex) == 0 && !(kMedia) ? RT_WAVES_BVH_LITE : RT_WAVES_BVH))
-#endif
-// Kernels built without MachineLICM (rt_kernel_nl.hip / rt_kernel64_nl.hip, compiled with
-// -mllvm -disable-machine-licm): the pass hoists the loop's binary64 constants (log, sincos and
-// texture polynomial coefficients, ...) out of the persistent lane loop into ~20-90 VGPRs, so the
-// heavier kernels sat at 2-3 waves or spilled (readme binary64 195 VGPRs -> 100: 0.65 -> 0.46 ms;
-// pawn+fog binary64 107 instead of 128 + spills).  The lightest kernels keep it: the Cornell box
-// (flat, constant textures, the diffuse materials) is 1.3 % slower without it and the bunny even
-// (profiles/r5/licm).  Every instantiation lives in exactly one of the two translation units.
-#ifndef RT_NOLICM_FLAT_LITE
-#define RT_NOLICM_FLAT_LITE 0  // (experiments: the binary64 Cornell kernel without MachineLICM too)
-#endif
-#ifndef RT_NOLICM_BVH_LITE
-#define RT_NOLICM_BVH_LITE 0  // (experiments: the bunny class without MachineLICM too)
-#endif
-#define RT_NOLICM_OF(kVar, kTex, kMedia, kMats, kInst)                                  \
-  ((kVar) == RT_VAR_FLAT ? (RT_F64 && (RT_NOLICM_FLAT_LITE || (kTex) != 0 || (kMedia) != 0 || (kMats))) \
-                         : (RT_NOLICM_BVH_LITE || (kTex) != 0 || (kMedia) != 0 || (kMats) || (kInst)))
+// One instantiation per kernel class (rt_kernel_class.h: the template parameters are KernelClass's
+// fields; launch bound, occupancy floor, stack stride and LDS layout are its functions of them)
 #ifndef RT_TU_NOLICM
 #define RT_TU_NOLICM 0
 #endif
-// kMedia of a variant code (rt_render_kernel's template parameter)
-#define RT_MEDIA_OF(variant) \
-  (((variant) & RT_VAR_MEDIA) == 0 ? 0 : ((variant) & RT_VAR_MEDIA_LATE) && ((variant) & RT_VAR_BASE) == RT_VAR_BVH ? 2 : 1)
-// BVH workgroup size of a kernel class: each workgroup stages its own LDS copy of the top BVH
-// nodes, so the fewer workgroups share a CU the more nodes each copy holds (pawn+fog and demo1
-// gain 6-13 % from staging).  The largest workgroup whose waves split evenly over the
-// CU's 4 SIMDs at the kernel's occupancy W (waves per SIMD): W = 3 -> 768 threads (one per CU),
-// 4 -> 1024 (one), 6 -> 768 (two), 8 -> 1024 (two); W = 5 / 7 keep 256.  Round 5 (profiles/r5/
-// bigwg): W = 4 at 1024 instead of 512 stages all of pawn+fog's surface nodes (binary64 476.5 ->
-// 428.1 ms; bunny even); W = 8 at 1024 instead of 256, FP32 demo1 39.35 -> 37.7 ms; 640 / 896
-// threads at W = 5 / 7 do not split evenly (10 / 14 waves per workgroup over 4 SIMDs): demo1
-// binary64 +36 %, pawn+fog FP32 +22 %, one workgroup per CU fits.  RT_BIG_WG=0: 256 everywhere.
-#ifndef RT_BIG_WG
-#define RT_BIG_WG 1
-#endif
-#ifndef RT_BLOCK_BVH_OF
-#define RT_BLOCK_BVH_OF(w) \
-  (RT_BIG_WG && ((w) == 3 || (w) == 6) ? 768 : RT_BIG_WG && ((w) == 4 || (w) == 8) ? 1024 : RT_BLOCK_BVH)
-#endif
-#define RT_BLOCK_OF(kVar, kTex, kMedia, kMats, kInst, kLeaf) \
-  ((kVar) == RT_VAR_FLAT ? RT_BLOCK : RT_BLOCK_BVH_OF(RT_WAVES_OF(kVar, kTex, kMedia, kMats, kInst, kLeaf)))
-// commit-aggregation slots per wave and pixels per slot of a kernel class (rt_internal.h)
-// (the wide slots: every binary64 flat class, and the FP32 flat classes without media —
-// rt_internal.h RT_AGG_*_FLAT_F64; rt_build.cpp rt_host_plan_work mirrors the choice)
-#define RT_AGG_WIDE_OF(kMedia) (RT_F64 || (kMedia) == 0)
-#define RT_AGG_SLOTS_FLAT_R(kMedia) (RT_AGG_WIDE_OF(kMedia) ? RT_AGG_SLOTS_FLAT_F64 : RT_AGG_SLOTS_FLAT)
-#define RT_AGG_PIX_FLAT_R(kMedia) (RT_AGG_WIDE_OF(kMedia) ? RT_AGG_PIX_FLAT_F64 : RT_AGG_PIX_FLAT)
-#define RT_AGG_SLOTS_OF(kVar, kMedia) ((kVar) == RT_VAR_FLAT ? RT_AGG_SLOTS_FLAT_R(kMedia) : RT_AGG_SLOTS_BVH)
-#define RT_AGG_PIX_OF(kVar, kMedia) ((kVar) == RT_VAR_FLAT ? RT_AGG_PIX_FLAT_R(kMedia) : RT_AGG_PIX_BVH)
-// kMedia: 0 none; 1 the media queries chained in the traversal loop; 2 the media events in the
-// shading phase (RT_VAR_MEDIA_LATE; rt_trace.h media_events_late)
-// kNarrow: the 1024-lane class at 512 lanes, for a scene whose stacks do not fit one 1024-lane
-// workgroup's LDS (RT_VAR_NARROW)
-#define RT_BLOCK_N(kVar, kTex, kMedia, kMats, kInst, kLeaf, kNarrow)                       \
-  ((kNarrow) && RT_BLOCK_OF(kVar, kTex, kMedia, kMats, kInst, kLeaf) == 1024 ? 512 \
-                                                                               : RT_BLOCK_OF(kVar, kTex, kMedia, kMats, kInst, kLeaf))
 template <int kVar, int kTex, int kMedia, bool kMats, bool kInst, int kLeaf, bool kNarrow = false>
-__global__ __launch_bounds__(RT_BLOCK_N(kVar, kTex, kMedia, kMats, kInst, kLeaf, kNarrow))
-__attribute__((amdgpu_waves_per_eu(RT_WAVES_OF(kVar, kTex, kMedia, kMats, kInst, kLeaf))))
+__global__ __launch_bounds__(rt_class_block(RT_F64, KernelClass{kVar, kTex, kMedia, kMats, kInst, kLeaf, kNarrow}))
+__attribute__((amdgpu_waves_per_eu(rt_class_waves(RT_F64, KernelClass{kVar, kTex, kMedia, kMats, kInst, kLeaf, kNarrow}))))
 void rt_render_kernel(KernelParams P) {
   extern __shared__ int smem[];
 #if defined(RT_WAVE_STAMPS)
   const unsigned long long t_start = wall_clock64();
 #endif
-  constexpr int kSlots = RT_AGG_SLOTS_OF(kVar, kMedia), kPix = RT_AGG_PIX_OF(kVar, kMedia);
-  // (the launch bound; a deep BVH's render may launch fewer lanes: host render_block)
+  constexpr KernelClass kC{kVar, kTex, kMedia, kMats, kInst, kLeaf, kNarrow};
+  constexpr int kSlots = rt_class_agg_slots(RT_F64, kC), kPix = rt_class_agg_pix(RT_F64, kC);
 #if defined(RT_BLOCK_RUNTIME)  // (experiment: the stack stride from blockDim; profiles/r5/bigwg, r6/nondet)
   const int block = (int)blockDim.x;
 #else
-  constexpr int block = RT_BLOCK_N(kVar, kTex, kMedia, kMats, kInst, kLeaf, kNarrow);
+  constexpr int block = rt_class_block(RT_F64, kC);
 #endif
   // (experiments, profiles/r6/nondet: one use of the launch-time workgroup size at a time)
 #if defined(RT_BLOCK_RUNTIME_STACK)
@@ -488,7 +325,7 @@ void rt_render_kernel(KernelParams P) {
 #else
   const int block_copy = block;
 #endif
-  constexpr int kAggBytes = AggGeom<kSlots, kPix>::kWaveBytes;
+  constexpr int kAggBytes = rt_class_agg_bytes(RT_F64, kC);
   const int waves = (int)(gridDim.x * (blockDim.x / 64));
   // wave-uniform (readfirstlane: the compiler cannot tell that threadIdx.x / 64 is), so the work
   // state and the slot pointers below live in SGPRs
@@ -498,10 +335,10 @@ void rt_render_kernel(KernelParams P) {
   // LDS: the lanes' item sums [RT_ACC_WORDS][block] (rt_trace.h AccLds; BVH kernels), the waves'
   // commit-aggregation slots (kAggBytes each), then (BVH kernels) [stack_depth + 1][block]
   // stack words (the last row a spare write target) and the top P.lds_nodes BVH nodes (64 B each)
-  using AccT = typename std::conditional<RT_ACC_LDS_OF(kVar, kMedia), AccLds, Acc>::type;
+  using AccT = typename std::conditional<rt_class_acc_lds(RT_F64, kC), AccLds, Acc>::type;
   AccT acc;
   int* smem_rest = smem;
-  if constexpr (RT_ACC_LDS_OF(kVar, kMedia)) {
+  if constexpr (rt_class_acc_lds(RT_F64, kC)) {
     acc = AccLds{reinterpret_cast<unsigned long long*>(smem) + threadIdx.x, (int)blockDim.x};
     smem_rest = smem + 2 * RT_ACC_WORDS(real) * (int)blockDim.x;
   }
@@ -551,8 +388,9 @@ void rt_render_kernel(KernelParams P) {
 #if !RT_TU_NOLICM  // (the main translation unit)
 // mean over spp (Ray.hs:232) from the fixed-point sums; NaN where a sample was non-finite.  One
 // thread per output word (blockIdx.y = the channel) and the FP32 scale from the host: the kernel
-// needs at most 8 VGPRs, so with two streams it fits beside the next frame's 7-wave FP32 render
-// grid (69 VGPRs, 8 left per SIMD lane) instead of waiting for that grid to drain.  frame_rows > 0:
+// needs at most 8 VGPRs.  The FP32 Cornell class (63 VGPRs at 8 waves per SIMD) takes every wave
+// slot, so beside the next frame's render grid the resolve's waves start as that grid's waves end,
+// not in registers it leaves free.  frame_rows > 0:
 // `out` is the whole frame and tile row t goes to its global row (the rt_exec row interleave; rows
 // past the image are padding and are skipped) — a multi-device scene's shards resolve straight into
 // the first device's frame over xGMI instead of being gathered by copies afterwards
@@ -585,112 +423,16 @@ __global__ __launch_bounds__(256) void rt_resolve_kernel(const long long* __rest
 }
 #endif
 
-#ifndef RT_LEAF_MEDIA
-#define RT_LEAF_MEDIA 1
-#endif
-// the leaf class (kLeaf) of the instantiation render_kernel_of selects for a variant: one-class
-// leaves only where render_kernel_media compiles them (the decoupled kernel without instances;
-// with media, triangle leaves and constant textures only)
-static int leaf_of(int variant) {
-  if ((variant & RT_VAR_BASE) != RT_VAR_BVH || (variant & RT_VAR_INST)) return 0;
-  if (variant & RT_VAR_MEDIA)
-    return RT_LEAF_MEDIA && !(variant & (RT_VAR_TEX | RT_VAR_NOISE)) && (variant & RT_VAR_LEAF_TRI) ? 1 : 0;
-  return (variant & RT_VAR_LEAF_TRI) ? 1 : (variant & RT_VAR_LEAF_SPHERE) ? 2 : 0;
-}
-// the workgroup of a variant's kernel (RT_BLOCK_OF of its class; RT_VAR_NARROW: half the
-// 1024-lane workgroup, rt_build.cpp rt_host_variant)
-static int render_block(int variant) {
-  const bool flat = (variant & RT_VAR_BASE) == RT_VAR_FLAT;
-  const int tex = (variant & RT_VAR_NOISE) ? 2 : (variant & RT_VAR_TEX) ? 1 : 0;
-  const int media = RT_MEDIA_OF(variant);
-  const bool mats = (variant & RT_VAR_MATS) != 0, inst = (variant & RT_VAR_INST) != 0;
-  const int b = RT_BLOCK_OF(flat ? RT_VAR_FLAT : RT_VAR_BVH, tex, media, mats, inst, leaf_of(variant));
-  return b == 1024 && (variant & RT_VAR_NARROW) ? 512 : b;
-}
-static bool acc_in_lds(int variant) {
-  return RT_ACC_LDS_OF((variant & RT_VAR_BASE) == RT_VAR_FLAT ? RT_VAR_FLAT : RT_VAR_BVH, (variant & RT_VAR_MEDIA) != 0);
-}
-// LDS besides the stacks and the staged nodes: the lanes' item sums and the aggregation slots
-static size_t render_fixed_lds(int variant) {
-  const bool flat = (variant & RT_VAR_BASE) == RT_VAR_FLAT;
-  const size_t acc = acc_in_lds(variant) ? (size_t)RT_ACC_WORDS(real) * 8 * render_block(variant) : 0;
-  const bool wide = RT_F64 || (variant & RT_VAR_MEDIA) == 0;
-  const size_t agg = (size_t)(!flat ? AggGeom<RT_AGG_SLOTS_BVH, RT_AGG_PIX_BVH>::kWaveBytes
-                              : wide ? AggGeom<RT_AGG_SLOTS_FLAT_F64, RT_AGG_PIX_FLAT_F64>::kWaveBytes
-                                     : AggGeom<RT_AGG_SLOTS_FLAT, RT_AGG_PIX_FLAT>::kWaveBytes) *
-                     (render_block(variant) / 64);
-  return acc + agg;
-}
-static size_t render_lds_bytes(int stack_depth, int variant, int lds_nodes) {
-  return render_fixed_lds(variant) + ((variant & RT_VAR_BASE) == RT_VAR_FLAT
-                    ? 0
-                    : (size_t)(stack_depth + 1) * render_block(variant) * sizeof(int) + (size_t)lds_nodes * 64);
-}
-
-// the kernel instantiation of a variant code (base variant | RT_VAR_TEX | RT_VAR_NOISE |
-// RT_VAR_MEDIA | RT_VAR_MATS): non-constant textures, noise textures, media and the materials
-// beyond lightSource / pitchBlack / lambertian are compiled only into the instantiations of
-// scenes that use them
-// (inlined everywhere it raises the register allocation of every scene's kernel: the Cornell
-// box is 4.8 % faster without the unused media code)
 typedef void (*render_fn)(KernelParams);
-// this translation unit's instantiation, or null when the other one holds it (RT_NOLICM_OF)
-template <int kVar, int kTex, int kMedia, bool kMats, bool kInst, int kLeaf>
-static render_fn kernel_here(int variant) {
-  if constexpr ((bool)(RT_NOLICM_OF(kVar, kTex, kMedia, kMats, kInst)) == (bool)RT_TU_NOLICM) {
-    if constexpr (RT_BLOCK_OF(kVar, kTex, kMedia, kMats, kInst, kLeaf) == 1024)  // (the narrow twin)
-      if (variant & RT_VAR_NARROW) return rt_render_kernel<kVar, kTex, kMedia, kMats, kInst, kLeaf, true>;
-    return rt_render_kernel<kVar, kTex, kMedia, kMats, kInst, kLeaf, false>;
-  } else {
-    (void)variant;
-    return nullptr;
-  }
-}
-template <int kVar, int kTex, int kMedia, bool kInst, int kLeaf>
-static render_fn render_kernel_mats(int variant) {
-  return (variant & RT_VAR_MATS) ? kernel_here<kVar, kTex, kMedia, true, kInst, kLeaf>(variant)
-                                 : kernel_here<kVar, kTex, kMedia, false, kInst, kLeaf>(variant);
-}
-template <int kVar, int kTex, bool kInst>
-static render_fn render_kernel_media(int variant) {
-  // one-class BVH leaves (RT_VAR_LEAF_*): the decoupled kernel without instances; with media,
-  // triangle leaves and constant textures only (pawn+fog)
-  if (variant & RT_VAR_MEDIA) {
-    // the decoupled kernel's media events: the traversal loop's query chain, or the shading phase
-    // (RT_VAR_MEDIA_LATE)
-    if constexpr (kVar == RT_VAR_BVH) {
-      if (variant & RT_VAR_MEDIA_LATE) {
-        if constexpr (!kInst && kTex == 0 && RT_LEAF_MEDIA)
-          if (variant & RT_VAR_LEAF_TRI) return render_kernel_mats<kVar, kTex, 2, kInst, 1>(variant);
-        return render_kernel_mats<kVar, kTex, 2, kInst, 0>(variant);
-      }
-    }
-    if constexpr (kVar == RT_VAR_BVH && !kInst && kTex == 0 && RT_LEAF_MEDIA)
-      if (variant & RT_VAR_LEAF_TRI) return render_kernel_mats<kVar, kTex, 1, kInst, 1>(variant);
-    return render_kernel_mats<kVar, kTex, 1, kInst, 0>(variant);
-  }
-  if constexpr (kVar == RT_VAR_BVH && !kInst) {
-    if (variant & RT_VAR_LEAF_TRI) return render_kernel_mats<kVar, kTex, 0, kInst, 1>(variant);
-    if (variant & RT_VAR_LEAF_SPHERE) return render_kernel_mats<kVar, kTex, 0, kInst, 2>(variant);
-  }
-  return render_kernel_mats<kVar, kTex, 0, kInst, 0>(variant);
-}
-template <int kVar, bool kInst>
-static render_fn render_kernel_flags(int variant) {
-  if (variant & RT_VAR_NOISE) return render_kernel_media<kVar, 2, kInst>(variant);
-  if (variant & RT_VAR_TEX) return render_kernel_media<kVar, 1, kInst>(variant);
-  return render_kernel_media<kVar, 0, kInst>(variant);
-}
-// two-level instancing (RT_VAR_INST) is compiled into the decoupled BVH kernel only
+// the instantiation of a variant's class (rt_kernel_class.h rt_class_of), or null when the other
+// translation unit holds it (rt_class_nolicm); the units instantiate exactly the compiled classes
 static render_fn render_kernel_this_tu(int variant) {
-  if (variant & RT_VAR_INST) return render_kernel_flags<RT_VAR_BVH, true>(variant);
-  switch (variant & RT_VAR_BASE) {
-    case RT_VAR_FLAT: return render_kernel_flags<RT_VAR_FLAT, false>(variant);
-#if RT_LOCKSTEP_KERNELS
-    case RT_VAR_BVH_LOCKSTEP: return render_kernel_flags<RT_VAR_BVH_LOCKSTEP, false>(variant);
-#endif
-    default: return render_kernel_flags<RT_VAR_BVH, false>(variant);
-  }
+  return rt_with_class(rt_class_of(RT_F64, variant), [](auto... k) -> render_fn {
+    constexpr KernelClass c{decltype(k)::value...};
+    if constexpr (rt_class_compiled(RT_F64, c) && rt_class_nolicm(RT_F64, c) == (bool)RT_TU_NOLICM)
+      return rt_render_kernel<c.var, c.tex, c.media, c.mats, c.inst, c.leaf, c.narrow>;
+    return nullptr;
+  });
 }
 // the kernels of the translation unit without MachineLICM (defined there)
 render_fn render_kernel_nolicm(int variant);
@@ -742,40 +484,27 @@ int rt_render_resident_blocks(const KernelParamsT<RT_NS::real>*, int device, int
                               int lds_nodes) {
   using namespace RT_NS;
   int per_cu = 0, cus = 0;
-  size_t lds = render_lds_bytes(stack_depth, variant, lds_nodes);
+  const KernelClass c = rt_class_of(RT_F64, variant);
+  size_t lds = rt_class_lds_bytes(RT_F64, c, stack_depth, lds_nodes);
   if (lds > 65536 && hipFuncSetAttribute((const void*)render_kernel_of(variant),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return -1;
   hipError_t e =
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_kernel_of(variant), render_block(variant), lds);
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_kernel_of(variant), rt_class_block(RT_F64, c), lds);
   if (e != hipSuccess) return -1;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return -1;
   if (per_cu < 1) per_cu = 1;
   return per_cu * cus;
 }
 
-// the render kernel's occupancy target (waves per SIMD) for a variant, and the LDS the lanes'
-// item sums take per workgroup: the host sizes the LDS node staging to what is left of the
-// workgroup's share of a CU's LDS at that occupancy (rt_api.hip ensure_precision)
-int rt_render_waves(const KernelParamsT<RT_NS::real>*, int variant) {
-  const bool flat = (variant & RT_VAR_BASE) == RT_VAR_FLAT;
-  const int tex = (variant & RT_VAR_NOISE) ? 2 : (variant & RT_VAR_TEX) ? 1 : 0;
-  const int media = RT_MEDIA_OF(variant);
-  const bool mats = (variant & RT_VAR_MATS) != 0, inst = (variant & RT_VAR_INST) != 0;
-  return RT_WAVES_OF(flat ? RT_VAR_FLAT : RT_VAR_BVH, tex, media, mats, inst, RT_NS::leaf_of(variant));
-}
-int rt_render_block(const KernelParamsT<RT_NS::real>*, int variant) { return RT_NS::render_block(variant); }
-int rt_render_acc_lds(const KernelParamsT<RT_NS::real>*, int variant) {
-  return (int)RT_NS::render_fixed_lds(variant);
-}
-
 int rt_launch_render(const KernelParamsT<RT_NS::real>& p, int grid_blocks, int variant, void* stream) {
   using namespace RT_NS;
   if (p.n_items <= 0 || grid_blocks <= 0) return 0;
-  const int block = render_block(variant);
+  const KernelClass c = rt_class_of(RT_F64, variant);
+  const int block = rt_class_block(RT_F64, c);
   long long need = ((long long)p.n_items + block - 1) / block;
   int grid = need < grid_blocks ? (int)need : grid_blocks;
-  size_t lds = render_lds_bytes(p.stack_depth, variant, p.lds_nodes);
+  size_t lds = rt_class_lds_bytes(RT_F64, c, p.stack_depth, p.lds_nodes);
   hipLaunchKernelGGL(render_kernel_of(variant), dim3(grid), dim3(block), lds, (hipStream_t)stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

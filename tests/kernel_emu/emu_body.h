@@ -35,39 +35,24 @@ struct Work {
   }
 };
 
-template <int kTex, int kMedia, bool kMats, class G>
-int run_loop(const RT_NS::KernelParams& P, int variant, G& g, const RT_NS::Trav& W) {
+// the lane loop of the variant's kernel class: the device kernels' own dispatch (rt_kernel_class.h
+// rt_class_of), so the emulator runs the instantiation the device runs
+template <class G>
+int run_variant(const RT_NS::KernelParams& P, int variant, G& g, const RT_NS::Trav& W) {
   // the item sums through the device kernels' LDS accumulator (one lane: stride 1)
   unsigned long long words[6] = {0, 0, 0, 0, 0, 0};
   RT_NS::AccLds acc{words, 1};
-  if (variant & RT_VAR_INST) return RT_NS::lane_loop_bvh<kTex, kMedia, kMats, true, 0>(P, g, W, P.prims, acc);
-  if ((variant & RT_VAR_BASE) == RT_VAR_BVH) {  // one-class leaves, as the device kernels
-    if (variant & RT_VAR_LEAF_TRI) return RT_NS::lane_loop_bvh<kTex, kMedia, kMats, false, 1>(P, g, W, P.prims, acc);
-    if ((variant & RT_VAR_LEAF_SPHERE) && !kMedia)
-      return RT_NS::lane_loop_bvh<kTex, kMedia, kMats, false, 2>(P, g, W, P.prims, acc);
-  }
-  switch (variant & RT_VAR_BASE) {
-    case RT_VAR_FLAT: return RT_NS::lane_loop_lockstep<true, kTex, kMedia != 0, kMats>(P, g, W, P.prims, acc);
-    case RT_VAR_BVH_LOCKSTEP:
-      return RT_NS::lane_loop_lockstep<false, kTex, kMedia != 0, kMats>(P, g, W, P.prims, acc);
-    default: return RT_NS::lane_loop_bvh<kTex, kMedia, kMats, false, 0>(P, g, W, P.prims, acc);
-  }
-}
-template <int kTex, class G>
-int run_flags(const RT_NS::KernelParams& P, int variant, G& g, const RT_NS::Trav& W) {
-  const int base = variant;
-  const bool media = (variant & RT_VAR_MEDIA) != 0, mats = (variant & RT_VAR_MATS) != 0;
-  // kMedia as the device kernels (rt_render_kernel.h RT_MEDIA_OF): 2 media events in the shading phase
-  if (media && (variant & RT_VAR_MEDIA_LATE) && (variant & RT_VAR_BASE) == RT_VAR_BVH)
-    return mats ? run_loop<kTex, 2, true>(P, base, g, W) : run_loop<kTex, 2, false>(P, base, g, W);
-  if (media) return mats ? run_loop<kTex, 1, true>(P, base, g, W) : run_loop<kTex, 1, false>(P, base, g, W);
-  return mats ? run_loop<kTex, 0, true>(P, base, g, W) : run_loop<kTex, 0, false>(P, base, g, W);
-}
-template <class G>
-int run_variant(const RT_NS::KernelParams& P, int variant, G& g, const RT_NS::Trav& W) {
-  if (variant & RT_VAR_NOISE) return run_flags<2>(P, variant, g, W);
-  if (variant & RT_VAR_TEX) return run_flags<1>(P, variant, g, W);
-  return run_flags<0>(P, variant, g, W);
+  KernelClass cls = rt_class_of(RT_F64, variant);
+  cls.narrow = false;  // (the workgroup size: nothing the lane loop sees)
+  return rt_with_class(cls, [&](auto... k) -> int {
+    constexpr KernelClass c{decltype(k)::value...};
+    if constexpr (!rt_class_compiled(RT_F64, c))
+      return 0;  // (no such kernel: rt_class_of names none of these)
+    else if constexpr (c.var == RT_VAR_BVH)
+      return RT_NS::lane_loop_bvh<c.tex, c.media, c.mats, c.inst, c.leaf>(P, g, W, P.prims, acc);
+    else
+      return RT_NS::lane_loop_lockstep<c.var == RT_VAR_FLAT, c.tex, c.media != 0, c.mats>(P, g, W, P.prims, acc);
+  });
 }
 
 void* worker(void* arg) {

@@ -11,6 +11,7 @@
 
 #include "../../include/rt.h"
 #include "../../raytrace_amd/csrc/rt_internal.h"
+#include "../../raytrace_amd/csrc/rt_kernel_class.h"
 // The device's FP32 reciprocal (v_rcp_f32) is within 1 ulp of 1/x, not correctly rounded:
 // rt_emu_set_rcp_ulps(k) makes the emulator's reciprocal the IEEE result moved k ulps (k < 0:
 // toward -inf), so the node test's conservativeness check covers both roundings the device can
