@@ -6,12 +6,25 @@
 //    b = nS.(u x (p-q)) = (p-q).wb) in binary64 and rounds it once to FP32,
 //  * builds one BVH per primitive set (surfaces, then each medium's boundary),
 //  * evaluates the camera set-up of Ray.hs:122-155 in binary64, in the reference's order.
+//
+// rt_host_build_scene is a driver over stages, each a free function of its inputs:
+//   1 read_knobs         the RT_AMD_* experiment knobs, once per call (nothing else reads the environment)
+//   2 validate_tables, validate_geometry   every check that needs only the caller's tables, and the scene flags
+//   3 gather_sets        each primitive's and placement's bounds, per set and per instanced object
+//   4 medium_aliases     media whose boundary is the surface set
+//   5 split_prefix       the large surface primitives tested before the BVH, and the set without them
+//   6 build_hierarchies  one BVH per set and per object: nodes, record order, roots, depths
+//   7 layout_records     flat sets grouped by class, box groups and their codes, slots
+//   8 fill_geometry, fill_shading   the device records of both precisions
+//   9 traversal_policy   the leaf kind and the exit percentages of the scene
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
+#include <utility>
 
 #include "../../include/rt.h"
 #include "rt_bvh.h"
@@ -202,38 +215,599 @@ struct BoxCodes {
   int ord_base, ord_code, gid_base, gid_code, prim_base, prim_code;
 };
 
-// The device records of one precision (rt_internal.h layout): primitives in `order` (slot
-// order for flat scenes, with class-grouped test copies), their materials, the textures,
-// motions, sphereUV frames, Perlin gradients and box groups.  The plane-shape frame of
+// ---- stage 1: the experiment knobs of the build (rt_internal.h rt_knob: null without
+// RT_AMD_EXPERIMENTS), read once per call; no other stage touches the environment
+struct BuildKnobs {
+  bool no_alias = false, no_prefix = false, no_box = false;
+  std::optional<double> prefix_area, prefix_shrink;
+  std::optional<int> leaf_max, leaf_exit_pct, trav_pct;  // clamped to their ranges
+};
+
+BuildKnobs read_knobs() {
+  BuildKnobs K;
+  auto on = [](const char* name) {
+    const char* e = rt_knob(name);
+    return e && atoi(e);
+  };
+  K.no_alias = on("RT_AMD_NO_ALIAS");    // experiments: always traverse boundaries
+  K.no_prefix = on("RT_AMD_NO_PREFIX");  // experiments: everything in the BVH
+  K.no_box = on("RT_AMD_NO_BOX");        // experiments: every face its own test
+  if (const char* e = rt_knob("RT_AMD_PREFIX_AREA")) K.prefix_area = atof(e);
+  if (const char* e = rt_knob("RT_AMD_PREFIX_SHRINK")) K.prefix_shrink = atof(e);
+  if (const char* e = rt_knob("RT_AMD_LEAF_MAX")) K.leaf_max = std::max(1, std::min(RT_FLAT_MAX, atoi(e)));
+  if (const char* e = rt_knob("RT_AMD_LEAF_EXIT_PCT")) K.leaf_exit_pct = std::max(1, std::min(100, atoi(e)));
+  if (const char* e = rt_knob("RT_AMD_TRAV_PCT")) K.trav_pct = std::max(0, std::min(100, atoi(e)));
+  return K;
+}
+
+// ---- stage 2: validation of the caller's tables (reads only `sc`; the first failing check, in
+// this order, is the error a scene reports)
+struct SceneFlags {
+  bool noise = false;      // some texture is a noise / marble texture
+  bool full_mats = false;  // some material is not lightSource / pitchBlack / lambertian
+  bool uv_tex = false;     // some material reads a non-constant texture
+};
+
+// two-level instancing: instanced objects (prims with set RT_SET_BLAS(b)) and their placements
+int n_objects(const rt_scene* sc) {
+  int n_blas = 0;
+  for (int i = 0; i < sc->n_prims; ++i)
+    if (sc->prims[i].set < 0) n_blas = std::max(n_blas, -sc->prims[i].set);
+  return n_blas;
+}
+
+int validate_tables(const rt_scene* sc, SceneFlags& flags, std::string& err) {
+  if (!sc) return fail(err, RT_E_INVALID, "null scene");
+  if (sc->n_prims < 0 || sc->n_media < 0 || sc->n_materials < 0 || sc->n_textures < 0 || sc->n_motions < 0 ||
+      sc->n_uvframes < 0)
+    return fail(err, RT_E_INVALID, "negative count");
+  if (sc->n_media > RT_MAX_MEDIA)
+    return fail(err, RT_E_UNSUPPORTED, "%d media (at most %d)", sc->n_media, RT_MAX_MEDIA);
+  if ((sc->n_prims && !sc->prims) || (sc->n_media && !sc->media) || (sc->n_materials && !sc->materials) ||
+      (sc->n_textures && !sc->textures) || (sc->n_motions && !sc->motions) || (sc->n_uvframes && !sc->uvframes))
+    return fail(err, RT_E_INVALID, "null array with nonzero count");
+  if (sc->n_texels < 0 || (sc->n_texels && !sc->texels)) return fail(err, RT_E_INVALID, "bad texel array");
+  for (int i = 0; i < sc->n_textures; ++i) {
+    const rt_texture& t = sc->textures[i];
+    if (t.kind < RT_TEX_CONSTANT || t.kind > RT_TEX_MARBLE)
+      return fail(err, RT_E_UNSUPPORTED, "texture %d: kind %d is not evaluated on the device", i, t.kind);
+    if (!finite_n(t.c0, 3) || !finite_n(t.c1, 3)) return fail(err, RT_E_INVALID, "texture %d: non-finite colour", i);
+    if (!finite_n(t.params, 8)) return fail(err, RT_E_INVALID, "texture %d: non-finite parameters", i);
+    if (t.kind == RT_TEX_IMAGE &&
+        (t.nu <= 0 || t.nv <= 0 || t.image < 0 || (long long)t.image + (long long)t.nu * t.nv > sc->n_texels))
+      return fail(err, RT_E_INVALID, "texture %d: image %dx%d at texel %d exceeds the %d texels", i, t.nu, t.nv,
+                  t.image, sc->n_texels);
+    if (t.kind == RT_TEX_NOISE && t.nu < 0) return fail(err, RT_E_INVALID, "texture %d: negative noise layers", i);
+    if (t.kind == RT_TEX_NOISE || t.kind == RT_TEX_MARBLE) flags.noise = true;
+  }
+  if (flags.noise) {
+    if (!sc->perlin) return fail(err, RT_E_INVALID, "noise / marble textures need rt_scene.perlin");
+    for (int a = 0; a < 3; ++a)
+      for (int k = 0; k < 256; ++k)
+        if (sc->perlin->perm[a][k] < 0 || sc->perlin->perm[a][k] > 255)
+          return fail(err, RT_E_INVALID, "perlin permutation entry out of [0, 255]");
+    for (int k = 0; k < 256; ++k)
+      if (!finite_n(sc->perlin->grad[k], 3)) return fail(err, RT_E_INVALID, "non-finite perlin gradient");
+  }
+  for (int i = 0; i < sc->n_materials; ++i) {
+    const rt_material& m = sc->materials[i];
+    if (m.kind != RT_MAT_LIGHT_SOURCE && m.kind != RT_MAT_PITCH_BLACK && m.kind != RT_MAT_LAMBERTIAN)
+      flags.full_mats = true;
+    if (m.texture >= 0 && m.texture < sc->n_textures && sc->textures[m.texture].kind != RT_TEX_CONSTANT)
+      flags.uv_tex = true;
+    if (m.kind < 0 || m.kind > RT_MAT_ANISOTROPIC)
+      return fail(err, RT_E_UNSUPPORTED, "material %d: kind %d", i, m.kind);
+    if (m.texture < 0 || m.texture >= sc->n_textures)
+      return fail(err, RT_E_INVALID, "material %d: bad texture index", i);
+  }
+  for (int k = 0; k < sc->n_media; ++k) {
+    const rt_medium& m = sc->media[k];
+    if (!(m.density > 0) || !std::isfinite(m.density))
+      return fail(err, RT_E_INVALID, "medium %d: density must be > 0", k);
+    if (m.material < 0 || m.material >= sc->n_materials) return fail(err, RT_E_INVALID, "medium %d: bad material", k);
+  }
+  return RT_OK;
+}
+
+// the placements, then the primitives (each with its motion)
+int validate_geometry(const rt_scene* sc, std::string& err) {
+  const int n_sets = 1 + sc->n_media;
+  if (sc->n_instances < 0 || (sc->n_instances && !sc->instances)) return fail(err, RT_E_INVALID, "bad instance array");
+  const int n_blas = n_objects(sc);
+  for (int k = 0; k < sc->n_instances; ++k) {
+    const rt_instance& I = sc->instances[k];
+    if (I.blas < 0 || I.blas >= n_blas) return fail(err, RT_E_INVALID, "instance %d: object %d has no leaves", k, I.blas);
+    if (I.material < -1 || I.material >= sc->n_materials) return fail(err, RT_E_INVALID, "instance %d: bad material", k);
+    if (!finite_n(I.m, 12)) return fail(err, RT_E_INVALID, "instance %d: non-finite transform", k);
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) {
+        const double d = I.m[a] * I.m[b] + I.m[4 + a] * I.m[4 + b] + I.m[8 + a] * I.m[8 + b];
+        if (std::fabs(d - (a == b ? 1.0 : 0.0)) > 1e-9)
+          return fail(err, RT_E_UNSUPPORTED, "instance %d: transform is not rigid (Geometry.hs:379-381)", k);
+      }
+  }
+  for (int i = 0; i < sc->n_prims; ++i) {
+    const rt_prim& p = sc->prims[i];
+    if (p.kind < RT_PRIM_SPHERE || p.kind > RT_PRIM_TRIANGLE) return fail(err, RT_E_INVALID, "prim %d: bad kind", i);
+    if (p.set >= n_sets) return fail(err, RT_E_INVALID, "prim %d: bad set %d", i, p.set);
+    if (p.set == 0 && (p.material < 0 || p.material >= sc->n_materials))
+      return fail(err, RT_E_INVALID, "prim %d: surface without a valid material", i);
+    if (p.set < 0 && (p.material < -1 || p.material >= sc->n_materials))
+      return fail(err, RT_E_INVALID, "prim %d: bad material", i);
+    if (p.motion >= sc->n_motions || p.uvframe >= sc->n_uvframes)
+      return fail(err, RT_E_INVALID, "prim %d: bad motion/uvframe index", i);
+    if (!finite_n(p.p, p.kind == RT_PRIM_SPHERE ? 4 : 9))
+      return fail(err, RT_E_INVALID, "prim %d: non-finite geometry", i);
+    if (p.motion >= 0) {
+      const rt_motion& m = sc->motions[p.motion];
+      if (!finite_n(m.v0, 3) || !finite_n(m.v1, 3)) return fail(err, RT_E_INVALID, "motion %d non-finite", p.motion);
+    }
+  }
+  return RT_OK;
+}
+
+// ---- stage 3: the primitive sets with their bounds
+double box_area(const double* lo, const double* hi) {
+  double d[3];
+  for (int a = 0; a < 3; ++a) d[a] = std::max(0.0, hi[a] - lo[a]);
+  return 2.0 * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0]);
+}
+struct Bounds {
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  void grow(const double* l, const double* h) {  // a box
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = std::min(lo[a], l[a]);
+      hi[a] = std::max(hi[a], h[a]);
+    }
+  }
+  void grow(const double* p) { grow(p, p); }  // a point
+  double area() const { return box_area(lo, hi); }
+  BuildPrim item(int index, int inst) const {  // the BVH builder's record of a primitive or placement
+    BuildPrim bp;
+    bp.index = index;
+    bp.inst = inst;
+    std::copy(lo, lo + 3, bp.lo);
+    std::copy(hi, hi + 3, bp.hi);
+    return bp;
+  }
+};
+Bounds bounds_of(const std::vector<BuildPrim>& prims) {
+  Bounds b;
+  for (const BuildPrim& p : prims) b.grow(p.lo, p.hi);
+  return b;
+}
+
+// a primitive's box, swept over its motion (std::fmin / fmax here, std::min / max in Bounds: they
+// differ on NaN and degenerate primitives reach this code)
+Bounds prim_bounds(const rt_scene* sc, const rt_prim& p) {
+  Bounds bp;
+  if (p.kind == RT_PRIM_SPHERE) {
+    double r = std::fabs(p.p[3]);
+    for (int a = 0; a < 3; ++a) {
+      bp.lo[a] = p.p[a] - r;
+      bp.hi[a] = p.p[a] + r;
+    }
+  } else {
+    for (int a = 0; a < 3; ++a) {
+      double q = p.p[a], u = p.p[3 + a], v = p.p[6 + a];
+      double c[4] = {q, q + u, q + v, q + u + v};
+      int nc = p.kind == RT_PRIM_PARALLELOGRAM ? 4 : 3;
+      bp.lo[a] = bp.hi[a] = c[0];
+      for (int k = 1; k < nc; ++k) {
+        bp.lo[a] = std::fmin(bp.lo[a], c[k]);
+        bp.hi[a] = std::fmax(bp.hi[a], c[k]);
+      }
+    }
+  }
+  if (p.motion >= 0) {
+    const rt_motion& m = sc->motions[p.motion];
+    for (int a = 0; a < 3; ++a) {
+      double lo = bp.lo[a], hi = bp.hi[a];
+      bp.lo[a] = std::fmin(lo + m.v0[a], lo + m.v1[a]);
+      bp.hi[a] = std::fmax(hi + m.v0[a], hi + m.v1[a]);
+    }
+  }
+  return bp;
+}
+
+struct PrimSets {
+  std::vector<std::vector<BuildPrim>> sets;       // [0] surfaces and placements, [k + 1] medium k's boundary
+  std::vector<std::vector<BuildPrim>> blas_sets;  // per instanced object, in object space
+};
+
+int gather_sets(const rt_scene* sc, PrimSets& P, std::string& err) {
+  const int n_blas = n_objects(sc);
+  P.sets.assign(1 + sc->n_media, {});
+  P.blas_sets.assign(n_blas, {});
+  std::vector<char> blas_all_mats(n_blas, 1);
+  for (int i = 0; i < sc->n_prims; ++i) {
+    const rt_prim& p = sc->prims[i];
+    if (p.set < 0 && p.material < 0) blas_all_mats[-1 - p.set] = 0;
+    (p.set < 0 ? P.blas_sets[-1 - p.set] : P.sets[p.set]).push_back(prim_bounds(sc, p).item(i, -1));
+  }
+  for (int k = 0; k < sc->n_media; ++k)
+    if (P.sets[k + 1].empty()) return fail(err, RT_E_INVALID, "medium %d has an empty boundary", k);
+  // every placement is one item of the surface set, boxed by its object's box under the transform
+  for (int k = 0; k < sc->n_instances; ++k) {
+    const rt_instance& I = sc->instances[k];
+    if (P.blas_sets[I.blas].empty()) return fail(err, RT_E_INVALID, "instance %d: object %d has no leaves", k, I.blas);
+    if (I.material < 0 && !blas_all_mats[I.blas])
+      return fail(err, RT_E_INVALID, "instance %d: a leaf of object %d has no material", k, I.blas);
+    const Bounds obj = bounds_of(P.blas_sets[I.blas]);
+    Bounds placed;
+    for (int c = 0; c < 8; ++c) {
+      const double x[3] = {(c & 1) ? obj.hi[0] : obj.lo[0], (c & 2) ? obj.hi[1] : obj.lo[1], (c & 4) ? obj.hi[2] : obj.lo[2]};
+      double w[3];
+      for (int a = 0; a < 3; ++a) w[a] = I.m[4 * a] * x[0] + I.m[4 * a + 1] * x[1] + I.m[4 * a + 2] * x[2] + I.m[4 * a + 3];
+      placed.grow(w);
+    }
+    P.sets[0].push_back(placed.item(-1, k));
+  }
+  return RT_OK;
+}
+
+// ---- stage 4: media whose boundary is, leaf for leaf in depth-first order, the surface set (DevMedium)
+std::vector<int> medium_aliases(const rt_scene* sc, const BuildKnobs& knobs) {
+  std::vector<int> alias(sc->n_media, 0);
+  // experiments: always traverse boundaries; the surface set also holds placements
+  if (knobs.no_alias || sc->n_instances > 0) return alias;
+  std::vector<std::vector<int>> by_set(1 + sc->n_media);
+  for (int i = 0; i < sc->n_prims; ++i)
+    if (sc->prims[i].set >= 0) by_set[sc->prims[i].set].push_back(i);  // instanced objects' leaves: not a set
+  for (auto& v : by_set)
+    std::stable_sort(v.begin(), v.end(), [&](int x, int y) { return sc->prims[x].order < sc->prims[y].order; });
+  auto same = [&](const rt_prim& a, const rt_prim& b) {
+    if (a.kind != b.kind || a.motion != b.motion || a.gid != b.gid || a.uvframe != b.uvframe) return false;
+    for (int j = 0; j < 9; ++j)
+      if (a.p[j] != b.p[j]) return false;
+    return true;
+  };
+  for (int k = 0; k < sc->n_media; ++k) {
+    const auto& a = by_set[0];
+    const auto& b = by_set[k + 1];
+    bool eq = !a.empty() && a.size() == b.size();
+    for (size_t j = 0; eq && j < a.size(); ++j) eq = same(sc->prims[a[j]], sc->prims[b[j]]);
+    alias[k] = eq ? 1 : 0;
+  }
+  return alias;
+}
+
+// the class of a primitive's test (rt_internal.h DevFlatSet): 0 parallelogram, 1 triangle, 2 sphere;
+// in a flat set the moving primitives of any kind are class 3
+int prim_class(const rt_prim& p, bool motion_is_a_class) {
+  if (motion_is_a_class && p.motion >= 0) return 3;
+  return p.kind == RT_PRIM_PARALLELOGRAM ? 0 : p.kind == RT_PRIM_TRIANGLE ? 1 : 2;
+}
+
+// ---- stage 5: the surface prefix
+// Large-primitive prefix of the surface set (BVH scenes).  Primitives whose box is a large
+// fraction of the whole set's (the Cornell walls around a mesh, demo1's ground sphere) overlap
+// almost every ray and sit at the top of any BVH; taken out of it, they are tested first by
+// the whole wave with wave-uniform records (scalar loads, like the flat kernel), and their
+// closest hit then bounds the traversal of the remaining BVH (rt_trace.h prefix_hits).  The
+// 64-bit closest-hit key carries each leaf's global depth-first order, so the result is the
+// same closest hit, tie for tie.  Only static primitives; grouped by class like a flat set.
+struct SurfacePrefix {
+  std::vector<int> prims;  // caller indices, class-grouped
+  int cnt[4] = {0, 0, 0, 0};  // per class (no moving primitives)
+  std::vector<BuildPrim> rest;  // the surface set without them
+};
+
+// marks the members of `set` (the whole surface set) that the prefix takes
+std::vector<char> select_prefix(const rt_scene* sc, const BuildKnobs& knobs, const std::vector<BuildPrim>& set) {
+  auto is_static = [&](const BuildPrim& b) { return b.inst < 0 && sc->prims[b.index].motion < 0; };
+  const double root_area = bounds_of(set).area();
+  const double frac = knobs.prefix_area.value_or(RT_PREFIX_AREA);
+  std::vector<std::pair<double, int>> big;  // (area, position in the set)
+  for (size_t j = 0; j < set.size(); ++j) {
+    const double a = box_area(set[j].lo, set[j].hi);
+    if (is_static(set[j]) && a >= frac * root_area) big.push_back({-a, (int)j});
+  }
+  std::stable_sort(big.begin(), big.end());
+  if (big.size() > RT_PREFIX_MAX) big.resize(RT_PREFIX_MAX);
+  std::vector<char> taken(set.size(), 0);
+  for (auto& b : big) taken[b.second] = 1;
+  // then outliers: a primitive that alone holds a face of the remaining set's box out by a
+  // lot (the Cornell light above the bunny: without it the BVH root shrinks to the bunny)
+  const double shrink = knobs.prefix_shrink.value_or(RT_PREFIX_SHRINK);
+  auto bounds_without = [&](int skip) {
+    Bounds r;
+    for (size_t j = 0; j < set.size(); ++j)
+      if (!taken[j] && (int)j != skip) r.grow(set[j].lo, set[j].hi);
+    return r;
+  };
+  for (int added = (int)big.size(); added < RT_PREFIX_MAX && shrink < 1.0; ++added) {
+    const Bounds all = bounds_without(-1);
+    const double a0 = all.area();
+    int best_j = -1;
+    double best_a = a0;
+    for (size_t j = 0; j < set.size(); ++j) {  // candidates: the primitives on the box's faces
+      const BuildPrim& b = set[j];
+      bool extreme = false;
+      for (int a = 0; a < 3; ++a) extreme = extreme || b.lo[a] == all.lo[a] || b.hi[a] == all.hi[a];
+      if (taken[j] || !extreme || !is_static(b)) continue;
+      const double a = bounds_without((int)j).area();
+      if (a < best_a) {
+        best_a = a;
+        best_j = (int)j;
+      }
+    }
+    if (best_j < 0 || !(best_a <= (1.0 - shrink) * a0)) break;
+    taken[best_j] = 1;
+  }
+  return taken;
+}
+
+SurfacePrefix split_prefix(const rt_scene* sc, const BuildKnobs& knobs, std::vector<BuildPrim> surface) {
+  SurfacePrefix out;
+  if ((int)surface.size() <= RT_FLAT_MAX + RT_PREFIX_MAX || knobs.no_prefix) {
+    out.rest = std::move(surface);
+    return out;
+  }
+  const std::vector<char> taken = select_prefix(sc, knobs, surface);
+  for (size_t j = 0; j < surface.size(); ++j) {
+    if (taken[j])
+      out.prims.push_back(surface[j].index);
+    else
+      out.rest.push_back(surface[j]);
+  }
+  auto cls = [&](int i) { return prim_class(sc->prims[i], false); };
+  std::stable_sort(out.prims.begin(), out.prims.end(), [&](int x, int y) { return cls(x) < cls(y); });
+  for (int i : out.prims) out.cnt[cls(i)]++;
+  return out;
+}
+
+// ---- stage 6: one BVH per set; primitives stored in leaf order, set after set (the prefix first)
+struct Hierarchies {
+  std::vector<float> nodes;    // HostScene::nodes
+  std::vector<int> order;      // caller index of every record: the prefix, each set's leaves, each object's
+  std::vector<int> roots;      // per set
+  std::vector<int> set_begin;  // per set, and the end of the last: its range of `order`
+  std::vector<int> blas_root;  // per instanced object
+  int surface_nodes = 0, max_depth = 0;
+};
+
+// the BVH of `prims` after the nodes and records so far
+BvhOut append_bvh(const std::vector<BuildPrim>& prims, int leaf_max, Hierarchies& H) {
+  BvhOut bo;
+  rt_build_bvh(prims, (int)(H.nodes.size() / 16), (int)H.order.size(), bo, leaf_max);
+  H.nodes.insert(H.nodes.end(), bo.nodes.begin(), bo.nodes.end());
+  H.order.insert(H.order.end(), bo.order.begin(), bo.order.end());
+  return bo;
+}
+
+Hierarchies build_hierarchies(const rt_scene* sc, const BuildKnobs& knobs, const PrimSets& P,
+                              const std::vector<int>& prefix) {
+  const int n_sets = (int)P.sets.size(), n_blas = (int)P.blas_sets.size();
+  Hierarchies H;
+  H.order = prefix;
+  H.roots.assign(n_sets, 0);
+  H.set_begin.assign(n_sets + 1, 0);
+  H.set_begin[0] = (int)prefix.size();
+  int surface_depth = 0;
+  for (int s = 0; s < n_sets; ++s) {
+    // leaves of at most 2 triangles / quads (bunny-Cornell 112 -> 107 ms, pawn+fog -1.2 % against
+    // 8 under the leaf-exit policy); sphere sets keep 8 (demo1 +0.6 % at 2)
+    bool spheres = true;
+    for (const BuildPrim& b : P.sets[s]) spheres = spheres && b.inst < 0 && sc->prims[b.index].kind == RT_PRIM_SPHERE;
+    const BvhOut a = append_bvh(P.sets[s], knobs.leaf_max.value_or(spheres ? RT_LEAF_MAX : 2), H);
+    H.roots[s] = a.root;
+    H.max_depth = std::max(H.max_depth, a.max_depth);
+    H.set_begin[s + 1] = (int)H.order.size();
+    if (s == 0) {
+      H.surface_nodes = (int)(H.nodes.size() / 16);
+      surface_depth = a.max_depth;
+    }
+  }
+  // instanced objects: one object-space BVH each (leaves of at most 2 primitives, as meshes),
+  // after the sets; the stack holds the world levels, the exit marker and the object's levels
+  H.blas_root.assign(n_blas, RT_EMPTY_ROOT);
+  int blas_depth = 0;
+  for (int b = 0; b < n_blas && sc->n_instances > 0; ++b) {
+    const BvhOut a = append_bvh(P.blas_sets[b], 2, H);
+    H.blas_root[b] = a.root;
+    blas_depth = std::max(blas_depth, a.max_depth);
+  }
+  if (sc->n_instances > 0) H.max_depth = std::max(H.max_depth, surface_depth + 1 + blas_depth + 1);
+  return H;
+}
+
+// ---- stage 7: layout of the tested records
+struct Layout {
+  std::vector<int> order;  // Hierarchies::order with flat sets class-grouped and box faces after their set's tests
+  DevFlatSet flat_sets[1 + RT_MAX_MEDIA] = {};
+  std::vector<BoxFound> boxes;
+  std::vector<BoxCodes> box_codes;
+  std::vector<int> slot_of;  // flat scenes: per record, its slot (else 0)
+};
+
+// the ranges of a class-grouped set at `first`: cnt[0] parallelograms, cnt[1] triangles, cnt[2]
+// spheres, cnt[3] moving primitives; no box groups
+DevFlatSet class_ranges(int first, const int* cnt) {
+  DevFlatSet F{};
+  F.first = first;
+  F.end_quad = F.first + cnt[0];
+  F.end_tri = F.end_quad + cnt[1];
+  F.end_sphere = F.end_tri + cnt[2];
+  F.end = F.end_sphere + cnt[3];
+  return F;
+}
+
+// group each flat set's single leaf by class (rt_internal.h DevFlatSet); stable within a class
+void group_by_class(const rt_scene* sc, const std::vector<int>& set_begin, Layout& L) {
+  auto cls = [&](int i) { return prim_class(sc->prims[i], true); };
+  for (size_t s = 0; s + 1 < set_begin.size(); ++s) {
+    int* b = L.order.data() + set_begin[s];
+    int* e = L.order.data() + set_begin[s + 1];
+    std::stable_sort(b, e, [&](int x, int y) { return cls(x) < cls(y); });
+    int cnt[4] = {0, 0, 0, 0};
+    for (int* it = b; it != e; ++it) cnt[cls(*it)]++;
+    L.flat_sets[s] = class_ranges(set_begin[s], cnt);
+  }
+}
+
+// box groups among a flat set's static parallelograms (or the surface prefix's), F's range of
+// L.order up to set_end: their faces move to the end of the range, after the tested classes (DevBox)
+void move_box_faces(const rt_scene* sc, int set_end, DevFlatSet& F, Layout& L) {
+  std::vector<int> quads(L.order.begin() + F.first, L.order.begin() + F.end_quad);
+  std::vector<BoxFound> found;
+  for (const BoxFound& B : find_boxes(sc, quads)) {
+    // the faces' key orders and gids must fit the 5-bit offset codes (slot spans are at
+    // most the order spans)
+    int olo = INT32_MAX, ohi = INT32_MIN, glo = INT32_MAX, ghi = INT32_MIN;
+    for (int f = 0; f < 6; ++f) {
+      if (B.face[f] < 0) continue;
+      const rt_prim& p = sc->prims[B.face[f]];
+      olo = std::min(olo, p.order);
+      ohi = std::max(ohi, p.order);
+      glo = std::min(glo, p.gid);
+      ghi = std::max(ghi, p.gid);
+    }
+    if ((long long)ohi - olo < RT_BOX_NO_FACE && (long long)ghi - glo < RT_BOX_NO_FACE) found.push_back(B);
+  }
+  F.box_first = F.box_end = (int)L.boxes.size();
+  if (found.empty()) return;
+  std::vector<char> in_box(sc->n_prims, 0);
+  std::vector<int> rest, faces;
+  for (const BoxFound& B : found) {
+    for (int f = 0; f < 6; ++f)
+      if (B.face[f] >= 0) {
+        in_box[B.face[f]] = 1;
+        faces.push_back(B.face[f]);
+      }
+    L.boxes.push_back(B);
+  }
+  for (int j = F.first; j < set_end; ++j)
+    if (!in_box[L.order[j]]) rest.push_back(L.order[j]);
+  const int removed = set_end - F.first - (int)rest.size();
+  std::copy(rest.begin(), rest.end(), L.order.begin() + F.first);
+  std::copy(faces.begin(), faces.end(), L.order.begin() + F.first + rest.size());
+  F.end_quad -= removed;
+  F.end_tri -= removed;
+  F.end_sphere -= removed;
+  F.end -= removed;
+  F.box_end = (int)L.boxes.size();
+}
+
+// flat scenes: slot of each primitive (rank of its order within the set) and slot -> index
+std::vector<int> slots(const rt_scene* sc, const std::vector<int>& order, const std::vector<int>& set_begin) {
+  std::vector<int> slot_of(order.size(), 0);
+  for (size_t s = 0; s + 1 < set_begin.size(); ++s) {
+    std::vector<int> pos;
+    for (int j = set_begin[s]; j < set_begin[s + 1]; ++j) pos.push_back(j);
+    std::stable_sort(pos.begin(), pos.end(),
+                     [&](int x, int y) { return sc->prims[order[x]].order < sc->prims[order[y]].order; });
+    for (size_t r = 0; r < pos.size(); ++r) slot_of[pos[r]] = set_begin[s] + (int)r;
+  }
+  return slot_of;
+}
+
+// box groups: the faces' key orders, gids and primitive indices as base + 5-bit codes
+int encode_boxes(const rt_scene* sc, bool flat, Layout& L, std::string& err) {
+  std::vector<int> pos_of(sc->n_prims, -1);
+  for (size_t j = 0; j < L.order.size(); ++j) pos_of[L.order[j]] = (int)j;
+  for (size_t b = 0; b < L.boxes.size(); ++b) {
+    const BoxFound& B = L.boxes[b];
+    BoxCodes d{};
+    int ord[6], gid[6], prm[6];
+    int ob = INT32_MAX, gb = INT32_MAX, pb = INT32_MAX;
+    for (int f = 0; f < 6; ++f) {
+      if (B.face[f] < 0) continue;
+      const int j = pos_of[B.face[f]];
+      ord[f] = flat ? L.slot_of[j] : sc->prims[B.face[f]].order;
+      gid[f] = sc->prims[B.face[f]].gid;
+      prm[f] = flat ? L.slot_of[j] : j;
+      ob = std::min(ob, ord[f]);
+      gb = std::min(gb, gid[f]);
+      pb = std::min(pb, prm[f]);
+    }
+    d.ord_base = ob;
+    d.gid_base = gb;
+    d.prim_base = pb;
+    bool fits = true;
+    for (int f = 0; f < 6; ++f) {
+      int oo = RT_BOX_NO_FACE, go = RT_BOX_NO_FACE, po = RT_BOX_NO_FACE;
+      if (B.face[f] >= 0) {
+        oo = ord[f] - ob;
+        go = gid[f] - gb;
+        po = prm[f] - pb;
+        fits = fits && oo < RT_BOX_NO_FACE && go < RT_BOX_NO_FACE && po < RT_BOX_NO_FACE;
+      }
+      d.ord_code |= oo << (5 * f);
+      d.gid_code |= go << (5 * f);
+      d.prim_code |= po << (5 * f);
+    }
+    if (!fits) return fail(err, RT_E_GENERIC, "box group %d: face offsets exceed the 5-bit codes", (int)b);
+    L.box_codes.push_back(d);
+  }
+  return RT_OK;
+}
+
+int layout_records(const rt_scene* sc, const BuildKnobs& knobs, bool flat, const SurfacePrefix& pre,
+                   const std::vector<int>& set_begin, std::vector<int> order, Layout& L, std::string& err) {
+  L.order = std::move(order);
+  if (!pre.prims.empty()) L.flat_sets[0] = class_ranges(0, pre.cnt);  // BVH scenes: the surface prefix
+  if (flat) group_by_class(sc, set_begin, L);
+  if (flat && !knobs.no_box) {
+    for (size_t s = 0; s + 1 < set_begin.size(); ++s) move_box_faces(sc, set_begin[s + 1], L.flat_sets[s], L);
+  } else if (!pre.prims.empty() && !knobs.no_box) {
+    move_box_faces(sc, (int)pre.prims.size(), L.flat_sets[0], L);
+  }
+  L.slot_of = flat ? slots(sc, L.order, set_begin) : std::vector<int>(L.order.size(), 0);
+  return encode_boxes(sc, flat, L, err);
+}
+
+// ---- stage 8: the device records
+// test order -> slot order (flat scenes: prim index = slot): row j of w values goes to row slot_of[j]
+template <class T>
+std::vector<T> to_slot_order(const std::vector<T>& rows, int w, const std::vector<int>& slot_of) {
+  std::vector<T> out(rows.size());
+  for (size_t j = 0; j < slot_of.size(); ++j)
+    std::copy(rows.begin() + w * j, rows.begin() + w * (j + 1), out.begin() + w * (size_t)slot_of[j]);
+  return out;
+}
+
+// material index per record (-1: medium boundary)
+std::vector<int> prim_materials(const rt_scene* sc, const Layout& L, bool flat) {
+  std::vector<int> mat(L.order.size(), -1);
+  for (size_t j = 0; j < mat.size(); ++j) {
+    const rt_prim& p = sc->prims[L.order[j]];
+    mat[j] = p.set <= 0 ? p.material : -1;
+  }
+  return flat ? to_slot_order(mat, 1, L.slot_of) : mat;
+}
+
+// The geometry records of one precision (rt_internal.h layout): the box groups and the primitives in
+// L.order (slot order for flat scenes, with class-grouped test copies).  The plane-shape frame of
 // Geometry.hs:117-131 (unit normal n, wa = v x nS, wb = nS x u, so that a = nS.((p-q) x v) =
 // (p-q).wa and b = nS.(u x (p-q)) = (p-q).wb) is computed in binary64 and rounded once to R.
 template <class R>
-void fill_records(const rt_scene* sc, const std::vector<int>& order, const std::vector<int>& slot_of, bool flat,
-                  const std::vector<BoxFound>& boxes, const std::vector<BoxCodes>& codes,
-                  const std::vector<int>& prim_mat, HostArraysT<R>& A) {
-  const int n = (int)order.size();
+void fill_geometry(const rt_scene* sc, const Layout& L, bool flat, HostArraysT<R>& A) {
+  const int n = (int)L.order.size();
   A.boxes.clear();
-  for (size_t b = 0; b < boxes.size(); ++b) {
+  for (size_t b = 0; b < L.boxes.size(); ++b) {
+    const BoxFound& B = L.boxes[b];
+    const BoxCodes& C = L.box_codes[b];
     DevBoxT<R> d;
     std::memset(&d, 0, sizeof d);
     // the slab offsets a_k . c in binary64, rounded once (the kernel's s_k = a_k . o - sc[k], three
     // FMAs per axis instead of the ray origin relative to the corner and a dot product)
-    for (int k = 0; k < 3; ++k) d.sc[k] = (R)dot(boxes[b].a[k], boxes[b].c);
-    put3(d.a0, boxes[b].a[0]);
-    put3(d.a1, boxes[b].a[1]);
-    put3(d.a2, boxes[b].a[2]);
-    d.ord_base = codes[b].ord_base;
-    d.ord_code = codes[b].ord_code;
-    d.gid_base = codes[b].gid_base;
-    d.gid_code = codes[b].gid_code;
-    d.prim_base = codes[b].prim_base;
-    d.prim_code = codes[b].prim_code;
+    for (int k = 0; k < 3; ++k) d.sc[k] = (R)dot(B.a[k], B.c);
+    put3(d.a0, B.a[0]);
+    put3(d.a1, B.a[1]);
+    put3(d.a2, B.a[2]);
+    d.ord_base = C.ord_base;
+    d.ord_code = C.ord_code;
+    d.gid_base = C.gid_base;
+    d.gid_code = C.gid_code;
+    d.prim_base = C.prim_base;
+    d.prim_code = C.prim_code;
     A.boxes.push_back(d);
   }
   A.prims.assign((size_t)n * 16, (R)0);
   A.prim_uv.assign((size_t)n * 6, (R)0);
   for (int j = 0; j < n; ++j) {
-    const rt_prim& p = sc->prims[order[j]];
+    const rt_prim& p = sc->prims[L.order[j]];
     R* f = A.prims.data() + 16 * (size_t)j;
     int kf = (p.kind == RT_PRIM_SPHERE ? 0 : p.kind == RT_PRIM_PARALLELOGRAM ? 1 : 2) |
              (p.motion >= 0 ? RT_FLAG_MOTION : 0);
@@ -258,22 +832,22 @@ void fill_records(const rt_scene* sc, const std::vector<int>& order, const std::
     }
     f[3] = ibits<R>(kf);
     f[7] = ibits<R>(p.gid);
-    f[11] = ibits<R>(flat ? slot_of[j] : p.order);
+    f[11] = ibits<R>(flat ? L.slot_of[j] : p.order);
     f[15] = ibits<R>(p.motion);
   }
   A.flat_recs.clear();
-  if (flat) {  // test order -> slot order for the shading arrays (prim index = slot)
-    A.flat_recs = A.prims;
-    std::vector<R> prims(A.prims.size()), uv(A.prim_uv.size());
-    for (int j = 0; j < n; ++j) {
-      const int k = slot_of[j];
-      std::copy(A.flat_recs.begin() + 16 * (size_t)j, A.flat_recs.begin() + 16 * (size_t)(j + 1),
-                prims.begin() + 16 * (size_t)k);
-      std::copy(A.prim_uv.begin() + 6 * (size_t)j, A.prim_uv.begin() + 6 * (size_t)(j + 1), uv.begin() + 6 * (size_t)k);
-    }
-    A.prims.swap(prims);
-    A.prim_uv.swap(uv);
+  if (flat) {  // the shading arrays in slot order, the test records as they are
+    A.flat_recs = std::move(A.prims);
+    A.prims = to_slot_order(A.flat_recs, 16, L.slot_of);
+    A.prim_uv = to_slot_order(A.prim_uv, 6, L.slot_of);
   }
+}
+
+// The shading tables of one precision: the materials (and one copy per record), the textures,
+// texels, Perlin gradients, motions, sphereUV frames and placements.
+template <class R>
+void fill_shading(const rt_scene* sc, const std::vector<int>& prim_mat, const std::vector<int>& blas_root,
+                  HostArraysT<R>& A) {
   A.mats.assign(sc->n_materials, DevMaterialT<R>{});
   for (int i = 0; i < sc->n_materials; ++i) {
     DevMaterialT<R>& d = A.mats[i];
@@ -318,10 +892,6 @@ void fill_records(const rt_scene* sc, const std::vector<int>& order, const std::
   for (int i = 0; i < sc->n_uvframes; ++i)
     for (int r = 0; r < 3; ++r)
       for (int c = 0; c < 3; ++c) A.uvframes[12 * (size_t)i + 4 * r + c] = (R)sc->uvframes[i].r[3 * r + c];
-}
-
-template <class R>
-void fill_instances(const rt_scene* sc, const std::vector<int>& blas_root, HostArraysT<R>& A) {
   A.instances.assign(sc->n_instances, DevInstanceT<R>{});
   for (int k = 0; k < sc->n_instances; ++k) {
     const rt_instance& I = sc->instances[k];
@@ -332,6 +902,58 @@ void fill_instances(const rt_scene* sc, const std::vector<int>& blas_root, HostA
     d.order = I.order;
     d.pad = 0;
   }
+}
+
+// ---- stage 9: the traversal policy of the scene
+struct TraversalPolicy {
+  int leaf_kind, leaf_exit_pct, leaf_exit_pct64, trav_exit_pct, trav_exit_pct64;
+};
+
+// BVH traversal policy (KernelParams::leaf_exit_pct), measured per scene class on MI355X:
+// testing leaves once a fifth to a third of the lanes hold one beats waiting for all of them
+// on triangle meshes (bunny-Cornell 138 -> 113 ms at 20-30 %, 124 at 10); with media in the queries 50-60 %
+// (pawn+fog 415 -> 385 ms; 30 % is no gain there); sphere-only leaves are cheapest tested all
+// together (demo1: 100 % best, 60 % +1 %)
+TraversalPolicy traversal_policy(const rt_scene* sc, const std::vector<int>& order, int n_prefix,
+                                 const std::vector<int>& roots, const std::vector<int>& set_begin,
+                                 const BuildKnobs& knobs) {
+  TraversalPolicy T;
+  const int n = (int)order.size();
+  bool spheres_only = true, static_tris = true, static_spheres = true;
+  for (int j = n_prefix; j < n; ++j) {
+    const rt_prim& p = sc->prims[order[j]];
+    spheres_only = spheres_only && p.kind == RT_PRIM_SPHERE;
+  }
+  // one-class leaves: the classes of the leaves the traversal reaches through BVH nodes (the
+  // surface set, and the media sets with a BVH); a medium set that is a single leaf (a fog
+  // sphere) is tested by the generic test (rt_trace.h test_leaf_generic)
+  for (size_t s = 0; s < roots.size(); ++s) {
+    if (s > 0 && roots[s] < 0) continue;
+    for (int j = set_begin[s]; j < set_begin[s + 1]; ++j) {
+      const rt_prim& p = sc->prims[order[j]];
+      static_tris = static_tris && p.kind == RT_PRIM_TRIANGLE && p.motion < 0;
+      static_spheres = static_spheres && p.kind == RT_PRIM_SPHERE && p.motion < 0;
+    }
+  }
+  // the leaf tests of the BVH kernel specialised to one primitive class (rt_trace.h trav_round
+  // kLeaf): bunny-Cornell 144.0 -> 139.7 ms binary64, demo1 63.9 -> 61.6 (profiles/r3/agg)
+  T.leaf_kind = n == n_prefix ? 0 : static_tris ? 1 : static_spheres ? 2 : 0;
+  // With media: round 5's media kernels (shading-phase events, binary64 in one 1024-lane
+  // workgroup per CU with the whole pawn BVH staged, FP32 at 6 waves) re-swept with the lane-loop
+  // exit below (profiles/r5/policy): FP32 leaves at 40 % and lane-loop exit 50 %, pawn+fog
+  // 275.5 -> 260.5 ms; binary64 55 % and 40 %, 428.3 -> 398.9 ms (round 4: 55 / 70 and 75).
+  // Sphere-only leaves: binary64 100 %; FP32 70 % since round 5 (demo1 37.73 -> 37.44 ms; binary64
+  // at 70 %: +0.6 %).
+  T.leaf_exit_pct = spheres_only ? 70 : sc->n_media > 0 ? 40 : 25;
+  T.leaf_exit_pct64 = spheres_only ? 100 : sc->n_media > 0 ? 55 : T.leaf_exit_pct;
+  if (knobs.leaf_exit_pct) T.leaf_exit_pct = T.leaf_exit_pct64 = *knobs.leaf_exit_pct;
+  // and the decoupled lane loop's exit (KernelParams::trav_exit_pct): demo1 49.2 -> 48.5 ms at 25 %
+  // (round 3), the bunny flat between 50 and 75, FP32 pawn+fog best at 50 since round 5's re-sweep
+  // (profiles/r5/policy; binary64 media scenes at 40 %, below)
+  T.trav_exit_pct = spheres_only ? 25 : 50;
+  T.trav_exit_pct64 = !spheres_only && sc->n_media > 0 ? 40 : T.trav_exit_pct;
+  if (knobs.trav_pct) T.trav_exit_pct = T.trav_exit_pct64 = *knobs.trav_pct;
+  return T;
 }
 
 }  // namespace
@@ -352,532 +974,61 @@ int rt_host_shard_rows(int height, const rt_exec* ex) {
 }
 
 int rt_host_build_scene(const rt_scene* sc, HostScene& S, std::string& err) {
-  if (!sc) return fail(err, RT_E_INVALID, "null scene");
-  if (sc->n_prims < 0 || sc->n_media < 0 || sc->n_materials < 0 || sc->n_textures < 0 || sc->n_motions < 0 ||
-      sc->n_uvframes < 0)
-    return fail(err, RT_E_INVALID, "negative count");
-  if (sc->n_media > RT_MAX_MEDIA)
-    return fail(err, RT_E_UNSUPPORTED, "%d media (at most %d)", sc->n_media, RT_MAX_MEDIA);
-  if ((sc->n_prims && !sc->prims) || (sc->n_media && !sc->media) || (sc->n_materials && !sc->materials) ||
-      (sc->n_textures && !sc->textures) || (sc->n_motions && !sc->motions) || (sc->n_uvframes && !sc->uvframes))
-    return fail(err, RT_E_INVALID, "null array with nonzero count");
-  if (sc->n_texels < 0 || (sc->n_texels && !sc->texels)) return fail(err, RT_E_INVALID, "bad texel array");
-  bool need_perlin = false;
-  for (int i = 0; i < sc->n_textures; ++i) {
-    const rt_texture& t = sc->textures[i];
-    if (t.kind < RT_TEX_CONSTANT || t.kind > RT_TEX_MARBLE)
-      return fail(err, RT_E_UNSUPPORTED, "texture %d: kind %d is not evaluated on the device", i, t.kind);
-    if (!finite_n(t.c0, 3) || !finite_n(t.c1, 3)) return fail(err, RT_E_INVALID, "texture %d: non-finite colour", i);
-    if (!finite_n(t.params, 8)) return fail(err, RT_E_INVALID, "texture %d: non-finite parameters", i);
-    if (t.kind == RT_TEX_IMAGE &&
-        (t.nu <= 0 || t.nv <= 0 || t.image < 0 || (long long)t.image + (long long)t.nu * t.nv > sc->n_texels))
-      return fail(err, RT_E_INVALID, "texture %d: image %dx%d at texel %d exceeds the %d texels", i, t.nu, t.nv,
-                  t.image, sc->n_texels);
-    if (t.kind == RT_TEX_NOISE && t.nu < 0) return fail(err, RT_E_INVALID, "texture %d: negative noise layers", i);
-    if (t.kind == RT_TEX_NOISE || t.kind == RT_TEX_MARBLE) need_perlin = true;
-  }
-  S.noise = need_perlin;
-  if (need_perlin) {
-    if (!sc->perlin) return fail(err, RT_E_INVALID, "noise / marble textures need rt_scene.perlin");
-    for (int a = 0; a < 3; ++a)
-      for (int k = 0; k < 256; ++k)
-        if (sc->perlin->perm[a][k] < 0 || sc->perlin->perm[a][k] > 255)
-          return fail(err, RT_E_INVALID, "perlin permutation entry out of [0, 255]");
-    for (int k = 0; k < 256; ++k)
-      if (!finite_n(sc->perlin->grad[k], 3)) return fail(err, RT_E_INVALID, "non-finite perlin gradient");
-  }
-  S.full_mats = false;
-  S.uv_tex = false;
-  for (int i = 0; i < sc->n_materials; ++i) {
-    const rt_material& m = sc->materials[i];
-    if (m.kind != RT_MAT_LIGHT_SOURCE && m.kind != RT_MAT_PITCH_BLACK && m.kind != RT_MAT_LAMBERTIAN) S.full_mats = true;
-    if (m.texture >= 0 && m.texture < sc->n_textures && sc->textures[m.texture].kind != RT_TEX_CONSTANT) S.uv_tex = true;
-    if (m.kind < 0 || m.kind > RT_MAT_ANISOTROPIC)
-      return fail(err, RT_E_UNSUPPORTED, "material %d: kind %d", i, m.kind);
-    if (m.texture < 0 || m.texture >= sc->n_textures)
-      return fail(err, RT_E_INVALID, "material %d: bad texture index", i);
-  }
-  for (int k = 0; k < sc->n_media; ++k) {
-    const rt_medium& m = sc->media[k];
-    if (!(m.density > 0) || !std::isfinite(m.density))
-      return fail(err, RT_E_INVALID, "medium %d: density must be > 0", k);
-    if (m.material < 0 || m.material >= sc->n_materials) return fail(err, RT_E_INVALID, "medium %d: bad material", k);
-  }
-  const int n_sets = 1 + sc->n_media;
-  // two-level instancing: instanced objects (prims with set RT_SET_BLAS(b)) and their placements
-  if (sc->n_instances < 0 || (sc->n_instances && !sc->instances)) return fail(err, RT_E_INVALID, "bad instance array");
-  int n_blas = 0;
-  for (int i = 0; i < sc->n_prims; ++i)
-    if (sc->prims[i].set < 0) n_blas = std::max(n_blas, -sc->prims[i].set);
-  for (int k = 0; k < sc->n_instances; ++k) {
-    const rt_instance& I = sc->instances[k];
-    if (I.blas < 0 || I.blas >= n_blas) return fail(err, RT_E_INVALID, "instance %d: object %d has no leaves", k, I.blas);
-    if (I.material < -1 || I.material >= sc->n_materials) return fail(err, RT_E_INVALID, "instance %d: bad material", k);
-    if (!finite_n(I.m, 12)) return fail(err, RT_E_INVALID, "instance %d: non-finite transform", k);
-    for (int a = 0; a < 3; ++a)
-      for (int b = 0; b < 3; ++b) {
-        const double d = I.m[a] * I.m[b] + I.m[4 + a] * I.m[4 + b] + I.m[8 + a] * I.m[8 + b];
-        if (std::fabs(d - (a == b ? 1.0 : 0.0)) > 1e-9)
-          return fail(err, RT_E_UNSUPPORTED, "instance %d: transform is not rigid (Geometry.hs:379-381)", k);
-      }
-  }
-  std::vector<std::vector<BuildPrim>> sets(n_sets), blas_sets(n_blas);
-  std::vector<char> blas_all_mats(n_blas, 1);
-  for (int i = 0; i < sc->n_prims; ++i) {
-    const rt_prim& p = sc->prims[i];
-    if (p.kind < RT_PRIM_SPHERE || p.kind > RT_PRIM_TRIANGLE) return fail(err, RT_E_INVALID, "prim %d: bad kind", i);
-    if (p.set >= n_sets) return fail(err, RT_E_INVALID, "prim %d: bad set %d", i, p.set);
-    if (p.set == 0 && (p.material < 0 || p.material >= sc->n_materials))
-      return fail(err, RT_E_INVALID, "prim %d: surface without a valid material", i);
-    if (p.set < 0 && (p.material < -1 || p.material >= sc->n_materials))
-      return fail(err, RT_E_INVALID, "prim %d: bad material", i);
-    if (p.set < 0 && p.material < 0) blas_all_mats[-1 - p.set] = 0;
-    if (p.motion >= sc->n_motions || p.uvframe >= sc->n_uvframes)
-      return fail(err, RT_E_INVALID, "prim %d: bad motion/uvframe index", i);
-    if (!finite_n(p.p, p.kind == RT_PRIM_SPHERE ? 4 : 9))
-      return fail(err, RT_E_INVALID, "prim %d: non-finite geometry", i);
-    BuildPrim bp;
-    bp.index = i;
-    if (p.kind == RT_PRIM_SPHERE) {
-      double r = std::fabs(p.p[3]);
-      for (int a = 0; a < 3; ++a) {
-        bp.lo[a] = p.p[a] - r;
-        bp.hi[a] = p.p[a] + r;
-      }
-    } else {
-      for (int a = 0; a < 3; ++a) {
-        double q = p.p[a], u = p.p[3 + a], v = p.p[6 + a];
-        double c[4] = {q, q + u, q + v, q + u + v};
-        int nc = p.kind == RT_PRIM_PARALLELOGRAM ? 4 : 3;
-        bp.lo[a] = bp.hi[a] = c[0];
-        for (int k = 1; k < nc; ++k) {
-          bp.lo[a] = std::fmin(bp.lo[a], c[k]);
-          bp.hi[a] = std::fmax(bp.hi[a], c[k]);
-        }
-      }
-    }
-    if (p.motion >= 0) {
-      const rt_motion& m = sc->motions[p.motion];
-      if (!finite_n(m.v0, 3) || !finite_n(m.v1, 3)) return fail(err, RT_E_INVALID, "motion %d non-finite", p.motion);
-      for (int a = 0; a < 3; ++a) {
-        double lo = bp.lo[a], hi = bp.hi[a];
-        bp.lo[a] = std::fmin(lo + m.v0[a], lo + m.v1[a]);
-        bp.hi[a] = std::fmax(hi + m.v0[a], hi + m.v1[a]);
-      }
-    }
-    if (p.set < 0)
-      blas_sets[-1 - p.set].push_back(bp);
-    else
-      sets[p.set].push_back(bp);
-  }
-  for (int k = 0; k < sc->n_media; ++k)
-    if (sets[k + 1].empty()) return fail(err, RT_E_INVALID, "medium %d has an empty boundary", k);
-  // every placement is one item of the surface set, boxed by its object's box under the transform
-  for (int k = 0; k < sc->n_instances; ++k) {
-    const rt_instance& I = sc->instances[k];
-    if (blas_sets[I.blas].empty()) return fail(err, RT_E_INVALID, "instance %d: object %d has no leaves", k, I.blas);
-    if (I.material < 0 && !blas_all_mats[I.blas])
-      return fail(err, RT_E_INVALID, "instance %d: a leaf of object %d has no material", k, I.blas);
-    double olo[3] = {INFINITY, INFINITY, INFINITY}, ohi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (const BuildPrim& b : blas_sets[I.blas])
-      for (int a = 0; a < 3; ++a) {
-        olo[a] = std::min(olo[a], b.lo[a]);
-        ohi[a] = std::max(ohi[a], b.hi[a]);
-      }
-    BuildPrim bp;
-    bp.index = -1;
-    bp.inst = k;
-    for (int a = 0; a < 3; ++a) {
-      bp.lo[a] = INFINITY;
-      bp.hi[a] = -INFINITY;
-    }
-    for (int c = 0; c < 8; ++c) {
-      const double x[3] = {(c & 1) ? ohi[0] : olo[0], (c & 2) ? ohi[1] : olo[1], (c & 4) ? ohi[2] : olo[2]};
-      for (int a = 0; a < 3; ++a) {
-        const double w = I.m[4 * a] * x[0] + I.m[4 * a + 1] * x[1] + I.m[4 * a + 2] * x[2] + I.m[4 * a + 3];
-        bp.lo[a] = std::min(bp.lo[a], w);
-        bp.hi[a] = std::max(bp.hi[a], w);
-      }
-    }
-    sets[0].push_back(bp);
-  }
+  const BuildKnobs knobs = read_knobs();
+  SceneFlags flags;
+  if (int rc = validate_tables(sc, flags, err)) return rc;
+  if (int rc = validate_geometry(sc, err)) return rc;
+  S.noise = flags.noise;
+  S.full_mats = flags.full_mats;
+  S.uv_tex = flags.uv_tex;
 
-  // media whose boundary is, leaf for leaf in depth-first order, the surface set (DevMedium)
-  std::vector<int> alias(sc->n_media, 0);
-  {
-    std::vector<std::vector<int>> by_set(n_sets);
-    for (int i = 0; i < sc->n_prims; ++i)
-      if (sc->prims[i].set >= 0) by_set[sc->prims[i].set].push_back(i);  // instanced objects' leaves: not a set
-    for (auto& v : by_set)
-      std::stable_sort(v.begin(), v.end(), [&](int x, int y) { return sc->prims[x].order < sc->prims[y].order; });
-    auto same = [&](const rt_prim& a, const rt_prim& b) {
-      if (a.kind != b.kind || a.motion != b.motion || a.gid != b.gid || a.uvframe != b.uvframe) return false;
-      for (int j = 0; j < 9; ++j)
-        if (a.p[j] != b.p[j]) return false;
-      return true;
-    };
-    for (int k = 0; k < sc->n_media; ++k) {
-      const auto& a = by_set[0];
-      const auto& b = by_set[k + 1];
-      bool eq = !a.empty() && a.size() == b.size();
-      for (size_t j = 0; eq && j < a.size(); ++j) eq = same(sc->prims[a[j]], sc->prims[b[j]]);
-      alias[k] = eq ? 1 : 0;
-    }
-  }
-  if (const char* e = rt_knob("RT_AMD_NO_ALIAS"))  // experiments: always traverse boundaries
-    if (atoi(e)) std::fill(alias.begin(), alias.end(), 0);
-  if (sc->n_instances > 0) std::fill(alias.begin(), alias.end(), 0);  // the surface set also holds placements
+  PrimSets P;
+  if (int rc = gather_sets(sc, P, err)) return rc;
+  const std::vector<int> alias = medium_aliases(sc, knobs);
+  SurfacePrefix pre = split_prefix(sc, knobs, std::move(P.sets[0]));
+  P.sets[0] = std::move(pre.rest);
 
-  // Large-primitive prefix of the surface set (BVH scenes).  Primitives whose box is a large
-  // fraction of the whole set's (the Cornell walls around a mesh, demo1's ground sphere) overlap
-  // almost every ray and sit at the top of any BVH; taken out of it, they are tested first by
-  // the whole wave with wave-uniform records (scalar loads, like the flat kernel), and their
-  // closest hit then bounds the traversal of the remaining BVH (rt_trace.h prefix_hits).  The
-  // 64-bit closest-hit key carries each leaf's global depth-first order, so the result is the
-  // same closest hit, tie for tie.  Only static primitives; grouped by class like a flat set.
-  std::vector<int> prefix;  // caller indices, class-grouped
-  int prefix_cnt[3] = {0, 0, 0};
-  {
-    bool want = (int)sets[0].size() > RT_FLAT_MAX + RT_PREFIX_MAX;
-    if (const char* e = rt_knob("RT_AMD_NO_PREFIX"))  // experiments: everything in the BVH
-      if (atoi(e)) want = false;
-    if (want) {
-      auto area = [](const double* lo, const double* hi) {
-        double d[3];
-        for (int a = 0; a < 3; ++a) d[a] = std::max(0.0, hi[a] - lo[a]);
-        return 2.0 * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0]);
-      };
-      double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-      for (const BuildPrim& b : sets[0])
-        for (int a = 0; a < 3; ++a) {
-          lo[a] = std::min(lo[a], b.lo[a]);
-          hi[a] = std::max(hi[a], b.hi[a]);
-        }
-      const double root_area = area(lo, hi);
-      double frac = RT_PREFIX_AREA;
-      if (const char* e = rt_knob("RT_AMD_PREFIX_AREA")) frac = atof(e);  // experiments
-      std::vector<std::pair<double, int>> big;  // (area, position in sets[0])
-      for (size_t j = 0; j < sets[0].size(); ++j) {
-        const BuildPrim& b = sets[0][j];
-        const double a = area(b.lo, b.hi);
-        if (b.inst < 0 && sc->prims[b.index].motion < 0 && a >= frac * root_area) big.push_back({-a, (int)j});
-      }
-      std::stable_sort(big.begin(), big.end());
-      if (big.size() > RT_PREFIX_MAX) big.resize(RT_PREFIX_MAX);
-      std::vector<char> taken(sets[0].size(), 0);
-      for (auto& b : big) taken[b.second] = 1;
-      // then outliers: a primitive that alone holds a face of the remaining set's box out by a
-      // lot (the Cornell light above the bunny: without it the BVH root shrinks to the bunny)
-      double shrink = RT_PREFIX_SHRINK;
-      if (const char* e = rt_knob("RT_AMD_PREFIX_SHRINK")) shrink = atof(e);  // experiments
-      for (int added = (int)big.size(); added < RT_PREFIX_MAX && shrink < 1.0; ++added) {
-        auto bounds_without = [&](int skip, double* l, double* h) {
-          for (int a = 0; a < 3; ++a) {
-            l[a] = INFINITY;
-            h[a] = -INFINITY;
-          }
-          for (size_t j = 0; j < sets[0].size(); ++j) {
-            if (taken[j] || (int)j == skip) continue;
-            for (int a = 0; a < 3; ++a) {
-              l[a] = std::min(l[a], sets[0][j].lo[a]);
-              h[a] = std::max(h[a], sets[0][j].hi[a]);
-            }
-          }
-        };
-        double l0[3], h0[3];
-        bounds_without(-1, l0, h0);
-        const double a0 = area(l0, h0);
-        int best_j = -1;
-        double best_a = a0;
-        for (size_t j = 0; j < sets[0].size(); ++j) {  // candidates: the primitives on the box's faces
-          const BuildPrim& b = sets[0][j];
-          bool extreme = false;
-          for (int a = 0; a < 3; ++a) extreme = extreme || b.lo[a] == l0[a] || b.hi[a] == h0[a];
-          if (taken[j] || !extreme || b.inst >= 0 || sc->prims[b.index].motion >= 0) continue;
-          double l[3], h[3];
-          bounds_without((int)j, l, h);
-          const double a = area(l, h);
-          if (a < best_a) {
-            best_a = a;
-            best_j = (int)j;
-          }
-        }
-        if (best_j < 0 || !(best_a <= (1.0 - shrink) * a0)) break;
-        taken[best_j] = 1;
-      }
-      auto cls = [&](int i) {
-        const int k = sc->prims[i].kind;
-        return k == RT_PRIM_PARALLELOGRAM ? 0 : k == RT_PRIM_TRIANGLE ? 1 : 2;
-      };
-      std::vector<BuildPrim> rest;
-      for (size_t j = 0; j < sets[0].size(); ++j) {
-        if (taken[j])
-          prefix.push_back(sets[0][j].index);
-        else
-          rest.push_back(sets[0][j]);
-      }
-      std::stable_sort(prefix.begin(), prefix.end(), [&](int x, int y) { return cls(x) < cls(y); });
-      for (int i : prefix) prefix_cnt[cls(i)]++;
-      sets[0].swap(rest);
-    }
-  }
-
-  // one BVH per set; primitives stored in leaf order, set after set (the prefix first)
-  std::vector<int> order(prefix);
-  std::vector<int> roots(n_sets), set_begin(n_sets + 1, 0);
-  int surface_depth = 0;
-  set_begin[0] = (int)prefix.size();
-  S.nodes.clear();
-  S.max_depth = 0;
-  for (int s = 0; s < n_sets; ++s) {
-    BvhOut bo;
-    // leaves of at most 2 triangles / quads (bunny-Cornell 112 -> 107 ms, pawn+fog -1.2 % against
-    // 8 under the leaf-exit policy); sphere sets keep 8 (demo1 +0.6 % at 2)
-    bool spheres = true;
-    for (const BuildPrim& b : sets[s]) spheres = spheres && b.inst < 0 && sc->prims[b.index].kind == RT_PRIM_SPHERE;
-    int leaf_max = spheres ? RT_LEAF_MAX : 2;
-    if (const char* e = rt_knob("RT_AMD_LEAF_MAX")) leaf_max = std::max(1, std::min(RT_FLAT_MAX, atoi(e)));
-    rt_build_bvh(sets[s], (int)(S.nodes.size() / 16), (int)order.size(), bo, leaf_max);
-    S.nodes.insert(S.nodes.end(), bo.nodes.begin(), bo.nodes.end());
-    order.insert(order.end(), bo.order.begin(), bo.order.end());
-    roots[s] = bo.root;
-    S.max_depth = std::max(S.max_depth, bo.max_depth);
-    set_begin[s + 1] = (int)order.size();
-    if (s == 0) {
-      S.surface_nodes = (int)(S.nodes.size() / 16);
-      surface_depth = bo.max_depth;
-    }
-  }
-  // instanced objects: one object-space BVH each (leaves of at most 2 primitives, as meshes),
-  // after the sets; the stack holds the world levels, the exit marker and the object's levels
-  std::vector<int> blas_root(n_blas, RT_EMPTY_ROOT);
-  int blas_depth = 0;
-  for (int b = 0; b < n_blas && sc->n_instances > 0; ++b) {
-    BvhOut bo;
-    rt_build_bvh(blas_sets[b], (int)(S.nodes.size() / 16), (int)order.size(), bo, 2);
-    S.nodes.insert(S.nodes.end(), bo.nodes.begin(), bo.nodes.end());
-    order.insert(order.end(), bo.order.begin(), bo.order.end());
-    blas_root[b] = bo.root;
-    blas_depth = std::max(blas_depth, bo.max_depth);
-  }
-  if (sc->n_instances > 0) S.max_depth = std::max(S.max_depth, surface_depth + 1 + blas_depth + 1);
-  if (S.nodes.size() / 16 >= (size_t)RT_MAX_NODES)
-    return fail(err, RT_E_UNSUPPORTED, "%zu BVH nodes exceed the kernels' 32-bit node offsets (%d)", S.nodes.size() / 16,
+  Hierarchies H = build_hierarchies(sc, knobs, P, pre.prims);
+  if (H.nodes.size() / 16 >= (size_t)RT_MAX_NODES)
+    return fail(err, RT_E_UNSUPPORTED, "%zu BVH nodes exceed the kernels' 32-bit node offsets (%d)", H.nodes.size() / 16,
                 RT_MAX_NODES);
-  if (S.max_depth > RT_STACK_DEPTH)
-    return fail(err, RT_E_STACK, "BVH depth %d exceeds the traversal stack (%d)", S.max_depth, RT_STACK_DEPTH);
-  const int n = (int)order.size();
-  S.flat = S.nodes.empty() && n <= RT_LDS_PRIMS_MAX && prefix.empty() && sc->n_instances == 0;
-  if (!prefix.empty()) {  // BVH scenes: flat_sets[0] describes the surface prefix
-    DevFlatSet& F = S.flat_sets[0];
-    F.first = 0;
-    F.end_quad = prefix_cnt[0];
-    F.end_tri = F.end_quad + prefix_cnt[1];
-    F.end_sphere = F.end_tri + prefix_cnt[2];
-    F.end = F.end_sphere;
-  }
-  if (S.flat) {
-    // group each set's single leaf by class (rt_internal.h DevFlatSet); stable within a class
-    auto cls = [&](int i) {
-      const rt_prim& p = sc->prims[i];
-      if (p.motion >= 0) return 3;
-      return p.kind == RT_PRIM_PARALLELOGRAM ? 0 : p.kind == RT_PRIM_TRIANGLE ? 1 : 2;
-    };
-    for (int s = 0; s < n_sets; ++s) {
-      int* b = order.data() + set_begin[s];
-      int* e = order.data() + set_begin[s + 1];
-      std::stable_sort(b, e, [&](int x, int y) { return cls(x) < cls(y); });
-      int cnt[4] = {0, 0, 0, 0};
-      for (int* it = b; it != e; ++it) cnt[cls(*it)]++;
-      DevFlatSet& F = S.flat_sets[s];
-      F.first = set_begin[s];
-      F.end_quad = F.first + cnt[0];
-      F.end_tri = F.end_quad + cnt[1];
-      F.end_sphere = F.end_tri + cnt[2];
-      F.end = F.end_sphere + cnt[3];
-      F.box_first = F.box_end = 0;
-      F.pad = 0;
-    }
-  }
-  // box groups among each flat set's static parallelograms (and the surface prefix): their
-  // faces move to the end of the set's range, after the tested classes (DevBox)
-  std::vector<BoxFound> boxes;
-  std::vector<int> box_face_pos;  // per box: position in `order` of its first face
-  {
-    bool want = true;
-    if (const char* e = rt_knob("RT_AMD_NO_BOX"))  // experiments: every face its own test
-      if (atoi(e)) want = false;
-    for (int s = 0; s < n_sets && want; ++s) {
-      if (!S.flat && !(s == 0 && !prefix.empty())) break;
-      DevFlatSet& F = S.flat_sets[s];
-      const int set_end = S.flat ? set_begin[s + 1] : (int)prefix.size();
-      std::vector<int> quads(order.begin() + F.first, order.begin() + F.end_quad);
-      std::vector<BoxFound> found;
-      for (const BoxFound& B : find_boxes(sc, quads)) {
-        // the faces' key orders and gids must fit the 5-bit offset codes (slot spans are at
-        // most the order spans)
-        int olo = INT32_MAX, ohi = INT32_MIN, glo = INT32_MAX, ghi = INT32_MIN;
-        for (int f = 0; f < 6; ++f) {
-          if (B.face[f] < 0) continue;
-          const rt_prim& p = sc->prims[B.face[f]];
-          olo = std::min(olo, p.order);
-          ohi = std::max(ohi, p.order);
-          glo = std::min(glo, p.gid);
-          ghi = std::max(ghi, p.gid);
-        }
-        if ((long long)ohi - olo < RT_BOX_NO_FACE && (long long)ghi - glo < RT_BOX_NO_FACE) found.push_back(B);
-      }
-      F.box_first = F.box_end = (int)boxes.size();
-      if (found.empty()) continue;
-      std::vector<char> in_box(sc->n_prims, 0);
-      for (const BoxFound& B : found)
-        for (int f = 0; f < 6; ++f)
-          if (B.face[f] >= 0) in_box[B.face[f]] = 1;
-      std::vector<int> rest, faces;
-      int removed = 0;
-      for (int j = F.first; j < set_end; ++j) {
-        if (in_box[order[j]]) {
-          ++removed;
-          continue;
-        }
-        rest.push_back(order[j]);
-      }
-      for (const BoxFound& B : found) {
-        box_face_pos.push_back(F.first + (int)rest.size() + (int)faces.size());
-        for (int f = 0; f < 6; ++f)
-          if (B.face[f] >= 0) faces.push_back(B.face[f]);
-        boxes.push_back(B);
-      }
-      std::copy(rest.begin(), rest.end(), order.begin() + F.first);
-      std::copy(faces.begin(), faces.end(), order.begin() + F.first + rest.size());
-      F.end_quad -= removed;
-      F.end_tri -= removed;
-      F.end_sphere -= removed;
-      F.end -= removed;
-      F.box_end = (int)boxes.size();
-    }
-  }
-  // flat scenes: slot of each primitive (rank of its order within the set) and slot -> index
-  std::vector<int> slot_of(n, 0);
-  if (S.flat) {
-    for (int s = 0; s < n_sets; ++s) {
-      std::vector<int> pos;
-      for (int j = set_begin[s]; j < set_begin[s + 1]; ++j) pos.push_back(j);
-      std::stable_sort(pos.begin(), pos.end(),
-                       [&](int x, int y) { return sc->prims[order[x]].order < sc->prims[order[y]].order; });
-      for (size_t r = 0; r < pos.size(); ++r) {
-        slot_of[pos[r]] = set_begin[s] + (int)r;
-      }
-    }
-  }
-  // box groups: the faces' key orders, gids and primitive indices as base + 5-bit codes
-  std::vector<BoxCodes> box_codes;
-  {
-    std::vector<int> pos_of(sc->n_prims, -1);
-    for (int j = 0; j < n; ++j) pos_of[order[j]] = j;
-    for (size_t b = 0; b < boxes.size(); ++b) {
-      const BoxFound& B = boxes[b];
-      BoxCodes d{};
-      int ord[6], gid[6], prm[6];
-      int ob = INT32_MAX, gb = INT32_MAX, pb = INT32_MAX;
-      for (int f = 0; f < 6; ++f) {
-        if (B.face[f] < 0) continue;
-        const int j = pos_of[B.face[f]];
-        ord[f] = S.flat ? slot_of[j] : sc->prims[B.face[f]].order;
-        gid[f] = sc->prims[B.face[f]].gid;
-        prm[f] = S.flat ? slot_of[j] : j;
-        ob = std::min(ob, ord[f]);
-        gb = std::min(gb, gid[f]);
-        pb = std::min(pb, prm[f]);
-      }
-      d.ord_base = ob;
-      d.gid_base = gb;
-      d.prim_base = pb;
-      bool fits = true;
-      for (int f = 0; f < 6; ++f) {
-        int oo = RT_BOX_NO_FACE, go = RT_BOX_NO_FACE, po = RT_BOX_NO_FACE;
-        if (B.face[f] >= 0) {
-          oo = ord[f] - ob;
-          go = gid[f] - gb;
-          po = prm[f] - pb;
-          fits = fits && oo < RT_BOX_NO_FACE && go < RT_BOX_NO_FACE && po < RT_BOX_NO_FACE;
-        }
-        d.ord_code |= oo << (5 * f);
-        d.gid_code |= go << (5 * f);
-        d.prim_code |= po << (5 * f);
-      }
-      if (!fits) return fail(err, RT_E_GENERIC, "box group %d: face offsets exceed the 5-bit codes", (int)b);
-      box_codes.push_back(d);
-    }
-  }
-  S.prim_mat.assign(n, -1);
-  for (int j = 0; j < n; ++j) S.prim_mat[j] = sc->prims[order[j]].set <= 0 ? sc->prims[order[j]].material : -1;
-  if (S.flat) {  // test order -> slot order for the shading arrays (prim index = slot)
-    std::vector<int> mat(S.prim_mat.size());
-    for (int j = 0; j < n; ++j) mat[slot_of[j]] = S.prim_mat[j];
-    S.prim_mat.swap(mat);
-  }
-  fill_records(sc, order, slot_of, S.flat, boxes, box_codes, S.prim_mat, S.f32);
-  fill_records(sc, order, slot_of, S.flat, boxes, box_codes, S.prim_mat, S.f64);
-  fill_instances(sc, blas_root, S.f32);
-  fill_instances(sc, blas_root, S.f64);
+  if (H.max_depth > RT_STACK_DEPTH)
+    return fail(err, RT_E_STACK, "BVH depth %d exceeds the traversal stack (%d)", H.max_depth, RT_STACK_DEPTH);
+  S.nodes = std::move(H.nodes);
+  S.n_nodes = (int)(S.nodes.size() / 16);
+  S.surface_nodes = H.surface_nodes;
+  S.max_depth = H.max_depth;
+  S.surface_root = H.roots[0];
+  S.n_prims = (int)H.order.size();
+  S.flat = S.nodes.empty() && S.n_prims <= RT_LDS_PRIMS_MAX && pre.prims.empty() && sc->n_instances == 0;
+
+  Layout L;
+  if (int rc = layout_records(sc, knobs, S.flat, pre, H.set_begin, std::move(H.order), L, err)) return rc;
+  std::copy(L.flat_sets, L.flat_sets + 1 + RT_MAX_MEDIA, S.flat_sets);
+  S.n_boxes = (int)L.boxes.size();
+
+  S.prim_mat = prim_materials(sc, L, S.flat);
+  fill_geometry(sc, L, S.flat, S.f32);
+  fill_geometry(sc, L, S.flat, S.f64);
+  fill_shading(sc, S.prim_mat, H.blas_root, S.f32);
+  fill_shading(sc, S.prim_mat, H.blas_root, S.f64);
   S.n_instances = sc->n_instances;
-  S.n_boxes = (int)boxes.size();
   S.perlin_perm.assign(3 * 256, 0);
   if (sc->perlin)
     for (int a = 0; a < 3; ++a)
       for (int k = 0; k < 256; ++k) S.perlin_perm[256 * a + k] = sc->perlin->perm[a][k];
-  S.surface_root = roots[0];
   S.n_media = sc->n_media;
   for (int k = 0; k < sc->n_media; ++k) {
-    S.f32.media[k] = DevMedium{(float)(-(1.0 / sc->media[k].density)), sc->media[k].material, roots[k + 1], alias[k]};
-    S.f64.media[k] = DevMediumT<double>{-(1.0 / sc->media[k].density), sc->media[k].material, roots[k + 1], alias[k]};
+    S.f32.media[k] = DevMedium{(float)(-(1.0 / sc->media[k].density)), sc->media[k].material, H.roots[k + 1], alias[k]};
+    S.f64.media[k] = DevMediumT<double>{-(1.0 / sc->media[k].density), sc->media[k].material, H.roots[k + 1], alias[k]};
   }
-  S.n_nodes = (int)(S.nodes.size() / 16);
-  // BVH traversal policy (KernelParams::leaf_exit_pct), measured per scene class on MI355X:
-  // testing leaves once a fifth to a third of the lanes hold one beats waiting for all of them
-  // on triangle meshes (bunny-Cornell 138 -> 113 ms at 20-30 %, 124 at 10); with media in the queries 50-60 %
-  // (pawn+fog 415 -> 385 ms; 30 % is no gain there); sphere-only leaves are cheapest tested all
-  // together (demo1: 100 % best, 60 % +1 %)
-  {
-    bool spheres_only = true, static_tris = true, static_spheres = true;
-    for (int j = (int)prefix.size(); j < n; ++j) {
-      const rt_prim& p = sc->prims[order[j]];
-      spheres_only = spheres_only && p.kind == RT_PRIM_SPHERE;
-    }
-    // one-class leaves: the classes of the leaves the traversal reaches through BVH nodes (the
-    // surface set, and the media sets with a BVH); a medium set that is a single leaf (a fog
-    // sphere) is tested by the generic test (rt_trace.h test_leaf_generic)
-    for (int s = 0; s < n_sets; ++s) {
-      if (s > 0 && roots[s] < 0) continue;
-      for (int j = set_begin[s]; j < set_begin[s + 1]; ++j) {
-        const rt_prim& p = sc->prims[order[j]];
-        static_tris = static_tris && p.kind == RT_PRIM_TRIANGLE && p.motion < 0;
-        static_spheres = static_spheres && p.kind == RT_PRIM_SPHERE && p.motion < 0;
-      }
-    }
-    // the leaf tests of the BVH kernel specialised to one primitive class (rt_trace.h trav_round
-    // kLeaf): bunny-Cornell 144.0 -> 139.7 ms binary64, demo1 63.9 -> 61.6 (profiles/r3/agg)
-    S.leaf_kind = n == (int)prefix.size() ? 0 : static_tris ? 1 : static_spheres ? 2 : 0;
-    // With media: round 5's media kernels (shading-phase events, binary64 in one 1024-lane
-    // workgroup per CU with the whole pawn BVH staged, FP32 at 6 waves) re-swept with the lane-loop
-    // exit below (profiles/r5/policy): FP32 leaves at 40 % and lane-loop exit 50 %, pawn+fog
-    // 275.5 -> 260.5 ms; binary64 55 % and 40 %, 428.3 -> 398.9 ms (round 4: 55 / 70 and 75).
-    // Sphere-only leaves: binary64 100 %; FP32 70 % since round 5 (demo1 37.73 -> 37.44 ms; binary64
-    // at 70 %: +0.6 %).
-    S.leaf_exit_pct = spheres_only ? 70 : sc->n_media > 0 ? 40 : 25;
-    S.leaf_exit_pct64 = spheres_only ? 100 : sc->n_media > 0 ? 55 : S.leaf_exit_pct;
-    if (const char* e = rt_knob("RT_AMD_LEAF_EXIT_PCT"))
-      S.leaf_exit_pct = S.leaf_exit_pct64 = std::max(1, std::min(100, atoi(e)));
-    // and the decoupled lane loop's exit (KernelParams::trav_exit_pct): demo1 49.2 -> 48.5 ms at 25 %
-    // (round 3), the bunny flat between 50 and 75, FP32 pawn+fog best at 50 since round 5's re-sweep
-    // (profiles/r5/policy; binary64 media scenes at 40 %, below)
-    S.trav_exit_pct = spheres_only ? 25 : 50;
-    S.trav_exit_pct64 = !spheres_only && sc->n_media > 0 ? 40 : S.trav_exit_pct;
-    if (const char* e = rt_knob("RT_AMD_TRAV_PCT"))
-      S.trav_exit_pct = S.trav_exit_pct64 = std::max(0, std::min(100, atoi(e)));
-  }
-  S.n_prims = n;
+
+  const TraversalPolicy T = traversal_policy(sc, L.order, (int)pre.prims.size(), H.roots, H.set_begin, knobs);
+  S.leaf_kind = T.leaf_kind;
+  S.leaf_exit_pct = T.leaf_exit_pct;
+  S.leaf_exit_pct64 = T.leaf_exit_pct64;
+  S.trav_exit_pct = T.trav_exit_pct;
+  S.trav_exit_pct64 = T.trav_exit_pct64;
   return RT_OK;
 }
 

@@ -66,3 +66,27 @@ def scene_info(world):
     if rc != 0:
         raise RuntimeError(f"rt_emu_scene_info failed {rc}: {lib().rt_emu_last_error().decode()}")
     return dict(zip(["n_nodes", "surface_nodes", "max_depth", "n_prims", "flat", "boxes", "prefix", "leaf_kind"], info.tolist()))
+
+
+_ARRAYS = ["prims", "prim_uv", "flat_recs", "motions", "uvframes", "texels", "perlin_grad", "prim_shade", "mats",
+           "texs", "boxes", "instances", "media"]
+# the items of rt_emu_scene_digest, in its order (rt_emu.cpp)
+DIGEST_ITEMS = (["nodes", "perlin_perm", "prim_mat", "flat_sets", "scalars"] + ["f32." + a for a in _ARRAYS]
+                + ["f64." + a for a in _ARRAYS])
+
+
+def scene_digest(world):
+    """(rc, error text, {item: [length, "fnv-1a hex"]}) of the host build of `world` (a Geometry or a
+    FlatScene): every array and scalar of HostScene in both precisions, so that two builders can be
+    compared byte for byte and a mismatch names the array.  rc != 0: the build's error, no items."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from raytrace_amd import _lib as R
+    from raytrace_amd.scene import FlatScene, flatten
+    flat = world if isinstance(world, FlatScene) else flatten(world)
+    sc = R.scene_struct(flat)
+    out = np.zeros(2 * len(DIGEST_ITEMS), np.uint64)
+    rc = lib().rt_emu_scene_digest(ctypes.byref(sc), out.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(len(out)))
+    if rc != 0:
+        return rc, lib().rt_emu_last_error().decode(), {}
+    return 0, "", {k: [int(out[2 * i]), f"{int(out[2 * i + 1]):016x}"] for i, k in enumerate(DIGEST_ITEMS)}

@@ -6,6 +6,7 @@
 
 #include <atomic>
 #include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -103,5 +104,97 @@ int rt_emu_scene_info(const rt_scene* sc, int* info) {
   info[6] = pre;
   info[7] = H.leaf_kind;
   return RT_OK;
+}
+}
+
+// Digest of the host build (test tooling): one (length, 64-bit FNV-1a) pair per item of HostScene,
+// every Dev* record hashed field by field (struct padding is unspecified).
+namespace {
+struct Fnv {
+  uint64_t h = 0xcbf29ce484222325ull;
+  template <class T>
+  void add(const T& v) {  // T: int, float or double
+    unsigned char b[sizeof(T)];
+    std::memcpy(b, &v, sizeof(T));
+    for (unsigned char c : b) h = (h ^ c) * 0x100000001b3ull;
+  }
+  template <class T, size_t N>
+  void add(const T (&a)[N]) {
+    for (const T& v : a) add(v);
+  }
+  template <class R>
+  void add(const DevMaterialT<R>& d) {
+    add(d.kind), add(d.tex), add(d.param), add(d.tex_const), add(d.c0), add(d.pad);
+  }
+  template <class R>
+  void add(const DevTextureT<R>& d) {
+    add(d.kind), add(d.nu), add(d.nv), add(d.off), add(d.c0), add(d.c1), add(d.prm), add(d.pad);
+  }
+  template <class R>
+  void add(const DevMediumT<R>& d) {
+    add(d.neg_inv_density), add(d.material), add(d.root), add(d.alias_surface);
+  }
+  void add(const DevFlatSet& d) {
+    add(d.first), add(d.end_quad), add(d.end_tri), add(d.end_sphere), add(d.end), add(d.box_first), add(d.box_end),
+        add(d.pad);
+  }
+  template <class R>
+  void add(const DevBoxT<R>& d) {
+    add(d.sc), add(d.ord_base), add(d.a0), add(d.ord_code), add(d.a1), add(d.gid_base), add(d.a2), add(d.gid_code),
+        add(d.prim_base), add(d.prim_code), add(d.pad);
+  }
+  template <class R>
+  void add(const DevInstanceT<R>& d) {
+    add(d.m), add(d.root), add(d.material), add(d.order), add(d.pad);
+  }
+};
+struct Digest {
+  uint64_t* out;
+  int n = 0;
+  template <class T>
+  void item(const T* p, size_t len) {
+    Fnv f;
+    for (size_t i = 0; i < len; ++i) f.add(p[i]);
+    out[2 * n] = len;
+    out[2 * n + 1] = f.h;
+    ++n;
+  }
+  template <class T>
+  void item(const std::vector<T>& v) { item(v.data(), v.size()); }
+};
+template <class R>
+void digest_arrays(const HostArraysT<R>& A, int n_media, Digest& D) {
+  D.item(A.prims), D.item(A.prim_uv), D.item(A.flat_recs), D.item(A.motions), D.item(A.uvframes), D.item(A.texels);
+  D.item(A.perlin_grad), D.item(A.prim_shade), D.item(A.mats), D.item(A.texs), D.item(A.boxes), D.item(A.instances);
+  D.item(A.media, (size_t)n_media);
+}
+}  // namespace
+
+extern "C" {
+// RT_EMU_DIGEST_ITEMS = 31 items, two words each (length in elements, hash), in this order
+// (tests/kernel_emu/emu.py DIGEST_ITEMS names them):
+//   nodes, perlin_perm, prim_mat, flat_sets (all 1 + RT_MAX_MEDIA),
+//   scalars (as ints, in declaration order: surface_root, n_media, n_nodes, n_prims, max_depth, n_boxes,
+//     surface_nodes, flat, noise, uv_tex, leaf_exit_pct, leaf_exit_pct64, trav_exit_pct, trav_exit_pct64,
+//     full_mats, n_instances, leaf_kind),
+//   then for f32 and for f64: prims, prim_uv, flat_recs, motions, uvframes, texels, perlin_grad, prim_shade,
+//     mats, texs, boxes, instances, media[0, n_media).
+// Returns the build's error (message: rt_emu_last_error) or RT_OK; n: words `out` holds (>= 62).
+int rt_emu_scene_digest(const rt_scene* sc, uint64_t* out, int n) {
+  if (!out || n < 2 * 31) return RT_E_INVALID;
+  HostScene H;
+  int rc = rt_host_build_scene(sc, H, g_err);
+  if (rc) return rc;
+  Digest D{out};
+  D.item(H.nodes), D.item(H.perlin_perm), D.item(H.prim_mat);
+  D.item(H.flat_sets, (size_t)(1 + RT_MAX_MEDIA));
+  const int scalars[] = {H.surface_root, H.n_media,         H.n_nodes,         H.n_prims,       H.max_depth,
+                         H.n_boxes,      H.surface_nodes,   H.flat,            H.noise,         H.uv_tex,
+                         H.leaf_exit_pct, H.leaf_exit_pct64, H.trav_exit_pct,  H.trav_exit_pct64, H.full_mats,
+                         H.n_instances,  H.leaf_kind};
+  D.item(scalars, sizeof scalars / sizeof scalars[0]);
+  digest_arrays(H.f32, H.n_media, D);
+  digest_arrays(H.f64, H.n_media, D);
+  return D.n == 31 ? RT_OK : RT_E_GENERIC;
 }
 }
