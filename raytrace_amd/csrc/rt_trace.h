@@ -180,14 +180,29 @@ __device__ __forceinline__ double sqrt_nonneg(double x) {
   s = __builtin_fma(d, h, s);
   return x == 0.0 || x == __builtin_huge_val() ? x : s;
 }
+}  // namespace rt_math64
+#endif
+#endif
+// (sincos_turns uses only fma and rint, so the host emulator build compiles it too: the emulator's
+// own RT_SINCOS_TURNS stays libm's, tests/device_probe runs this algorithm on both sides)
+#ifndef RT_MATH64_SINCOS_DEFINED
+#define RT_MATH64_SINCOS_DEFINED
+#ifdef RT_HOST_EMU
+#define RT_MATH64_FN static inline
+#define RT_MATH64_TAB static
+#else
+#define RT_MATH64_FN __device__ __forceinline__
+#define RT_MATH64_TAB __device__
+#endif
+namespace rt_math64 {
 // sin / cos of 2 pi u for u in [0, 1) (the samplers' angles; u has 24 random bits): u = k / 128 +
 // b with k = rint(128 u) and |b| <= 1/256 exact, (sin, cos)(2 pi k / 128) from a correctly rounded
 // table (rt_sincos_table.h, 2 KB, L1-resident), sin / cos (2 pi b) by short Taylor polynomials
 // (|2 pi b| <= 0.0246: truncation < 1e-17), combined by the angle-addition formulas
-__device__ const double rt_sincos_tab[2 * RT_SINCOS_TABLE_N] = RT_SINCOS_TABLE_INIT;
+RT_MATH64_TAB const double rt_sincos_tab[2 * RT_SINCOS_TABLE_N] = RT_SINCOS_TABLE_INIT;
 // (a table-free version — quadrant reduction and fdlibm's minimax kernels, 3.25 ulp — ran Cornell
 // 4.89 -> 5.42 ms: the table's two loads cost less than the longer polynomials; profiles/r5/variants)
-__device__ __forceinline__ void sincos_turns(double u, double* sn, double* cs) {
+RT_MATH64_FN void sincos_turns(double u, double* sn, double* cs) {
   const double kq = __builtin_rint(u * (double)RT_SINCOS_TABLE_N);
   const double b = __builtin_fma(kq, -1.0 / RT_SINCOS_TABLE_N, u);
   const int k = (int)kq & (RT_SINCOS_TABLE_N - 1);
@@ -203,7 +218,6 @@ __device__ __forceinline__ void sincos_turns(double u, double* sn, double* cs) {
   *cs = __builtin_fma(ca, cb, -(sa * sb));
 }
 }  // namespace rt_math64
-#endif
 #endif
 #else
 #define RT_NS rtk
@@ -949,14 +963,18 @@ RT_FN long long to_fixed(real x, bool& bad) {
     bad = true;
     return 0;
   }
-  // x * 2^32 without FP64: for x >= 0 (radiance) the integer part and the fraction are exact
-  // in FP32 (x - floor(x) is exact) and the fraction scaled by 2^32 is exact, so two 32-bit
-  // conversions give exactly trunc(x * 2^32).  (Negative inputs, possible only with negative
-  // user colours, are within 2^-25 relative of it.)
-  const real fl = RFLOOR(x);
+  // x * 2^32 without FP64: for |x| the integer part and the fraction are exact in FP32 (|x| -
+  // floor |x| is exact) and the fraction scaled by 2^32 is exact, so two 32-bit conversions give
+  // exactly trunc(|x| * 2^32); the sign is put back on the integer, so negative inputs (possible
+  // only with negative user colours) are exact too.  (x - floor(x) for x < 0 is not: for -1 < x < 0
+  // it rounds to 24 bits next to 1, an error of 2^-25 absolute, any size relative to x;
+  // tests/test_device_probe.py test_fixed_point_words.)
+  const real ax = RABS(x);
+  const real fl = RFLOOR(ax);
   const long long hi = (long long)(int)fl;
-  const unsigned lo = (unsigned)((x - fl) * RL(4294967296.0));
-  return (long long)((unsigned long long)hi << 32) + (long long)lo;
+  const unsigned lo = (unsigned)((ax - fl) * RL(4294967296.0));
+  const long long m = (long long)((unsigned long long)hi << 32) + (long long)lo;
+  return x < RL(0.0) ? -m : m;
 }
 RT_FN void acc_add(Acc& A, int c, real x, bool& bad) { A.hi[c] += to_fixed(x, bad); }
 #endif

@@ -27,17 +27,36 @@ static inline float rt_emu_rcpf(float x) {
   return r;
 }
 #define RT_RCPF(x) rt_emu_rcpf(x)
+// The element-wise probes of tests/device_probe/probe_body.h on host arrays (rt_emu_probe_<name>_f32
+// / _f64): the same entry points tests/device_probe/rt_probe.hip gives the device, as plain loops.
+#define RT_PROBE_CAT2(a, b) a##b
+#define RT_PROBE_CAT(a, b) RT_PROBE_CAT2(a, b)
+#define RT_PROBE_DEFINE(name, params, args)                                                      \
+  extern "C" int RT_PROBE_CAT(rt_emu_probe_##name, RT_PROBE_SFX)(int n, RT_PROBE_UNPACK params) { \
+    for (int i = 0; i < n; ++i) pb_##name(i, RT_PROBE_UNPACK args);                              \
+    return 0;                                                                                    \
+  }
 #define RT_F64 0
 #include "../../raytrace_amd/csrc/rt_trace.h"
 namespace emu32 {
 #include "emu_body.h"
 }  // namespace emu32
+#define RT_PROBE_SFX _f32
+namespace probe32 {
+#include "../device_probe/probe_body.h"
+}  // namespace probe32
+#undef RT_PROBE_SFX
 #undef RT_F64
 #define RT_F64 1
 #include "../../raytrace_amd/csrc/rt_trace.h"
 namespace emu64 {
 #include "emu_body.h"
 }  // namespace emu64
+#define RT_PROBE_SFX _f64
+namespace probe64 {
+#include "../device_probe/probe_body.h"
+}  // namespace probe64
+#undef RT_PROBE_SFX
 
 namespace rt_emu {
 thread_local long long counters[4];
@@ -64,6 +83,12 @@ int rt_emu_render(const rt_camera_settings* cs, const rt_scene* sc, uint64_t see
 
 extern "C" {
 void rt_emu_set_rcp_ulps(int k) { rt_emu::rcp_ulps = k; }
+
+// the sin / cos table of rt_math64::sincos_turns as the compiler reads it: 2 * 128 doubles
+int rt_emu_probe_sincos_table(double* out) {
+  for (int k = 0; k < 2 * RT_SINCOS_TABLE_N; ++k) out[k] = rt_math64::rt_sincos_tab[k];
+  return RT_SINCOS_TABLE_N;
+}
 
 // The binary64 kernel's FP32 BVH node test (rtk64::prep_ray + node_slabs_f32) for n rays, each
 // against one box given as both children of a node: box = (xmin, xmax, ymin, ymax, zmin, zmax)

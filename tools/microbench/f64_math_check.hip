@@ -2,6 +2,8 @@
 // rt_math64: v_rcp_f64 / v_rsq_f64 with a third-order correction, sin / cos of 2 pi u) against the IEEE /
 // OCML results on the device.  Prints one JSON object: per function the largest difference in
 // units in the last place and the fraction of inputs that differ at all.
+// A one-off measurement (profiles/r2/f64_math_check.json): the accuracy itself is now guarded by
+// tests/test_device_probe.py, which compares the same functions with IEEE and long-double references.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
