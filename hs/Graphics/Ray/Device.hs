@@ -39,6 +39,8 @@ module Graphics.Ray.Device
   ( -- * The drop-in
     raytrace, raytraceWith, DeviceOptions(..), defaultDeviceOptions, Precision(..), RenderError(..)
   , renderOnDevice, deviceCount
+    -- * Progressive rendering on a film (rt.h rt_film_*): stop when the noise is low enough
+  , raytraceUntil, renderUntilOnDevice
     -- * 8-bit output encoded on the device (writeImage / writeImageSqrt of a render, Ray.hs:248-260)
   , Encoding(..), renderImage8, raytraceToFile
     -- * Geometry (Geometry.hs:5-16)
@@ -547,6 +549,21 @@ foreign import ccall unsafe "rt_image_height"
   c_rt_image_height :: Ptr RtCamera -> IO CInt
 foreign import ccall safe "rt_device_count"
   c_rt_device_count :: IO CInt
+-- the resident scene and the progressive film on it (rt.h rt_film_*; opaque handles)
+foreign import ccall safe "rt_scene_create"
+  c_rt_scene_create :: Ptr RtScene -> Int32 -> Ptr (Ptr ()) -> IO CInt
+foreign import ccall safe "rt_scene_destroy"
+  c_rt_scene_destroy :: Ptr () -> IO CInt
+foreign import ccall safe "rt_film_create"
+  c_rt_film_create :: Ptr () -> Ptr RtCamera -> Word64 -> Ptr RtExec -> Ptr (Ptr ()) -> IO CInt
+foreign import ccall safe "rt_film_destroy"
+  c_rt_film_destroy :: Ptr () -> IO CInt
+foreign import ccall safe "rt_film_add"
+  c_rt_film_add :: Ptr () -> Int32 -> Ptr () -> IO CInt
+foreign import ccall safe "rt_film_read"
+  c_rt_film_read :: Ptr () -> Ptr () -> IO CInt
+foreign import ccall safe "rt_film_noise"
+  c_rt_film_noise :: Ptr () -> Ptr CFloat -> Ptr CDouble -> IO CInt
 
 -- Struct layouts of include/rt.h (x86-64).  tests/test_abi.py checks every `-- LAYOUT` line
 -- against the C compiler's offsetof / sizeof.
@@ -913,3 +930,98 @@ raytraceWith opts settings world gen =
     Left e | fallback e -> R.raytrace settings (toReferenceRandom world) gen
            | otherwise -> error ("Graphics.Ray.Device.raytrace: rt_render failed: " ++ show e)
 {-# NOINLINE raytraceWith #-}
+
+-- | A failing library call as a 'RenderError' (the thread's rt_last_error message).
+libraryError :: CInt -> IO (Either RenderError a)
+libraryError rc = Left . LibraryError (fromIntegral rc) <$> (c_rt_last_error >>= peekCString)
+
+-- | Render progressively on one GPU through a film (rt.h rt_film_*): passes of @batch@ samples
+-- until the frame's noise figure (rt_film_noise, checked from the second pass on) is at most
+-- @target@ or cs_samplesPerPixel samples are reached (the last pass is cut to fit).  Returns the
+-- image and the samples per pixel it holds; the image is bit-identical to rt_render's at that
+-- sample count.  The film lives on the first device of 'doDevices' (device 0 by default).
+renderUntilOnDevice :: DeviceOptions -> R.CameraSettings -> Geometry m Material -> StdGen -> Double -> Int
+                    -> IO (Either RenderError (A.Matrix A.S Color, Int))
+renderUntilOnDevice opts settings world gen target batch =
+  case (geoDesc world, reifyBackground (R.cs_background settings)) of
+    (Just desc, Just bg) -> do
+      tagged <- tagShared desc
+      case flatten tagged of
+        Nothing -> pure (Left NotReifiable)
+        Just flat -> do
+          let dev = case doDevices opts of { Just (d : _) -> d; _ -> 0 }
+          withCamera settings bg $ \cam ->
+            withFlatScene flat $ \sc ->
+            withExec opts Nothing [] $ \ex -> do      -- n_devices = 0: a film lives on one device
+              pokeI32 ex 0 (fromIntegral dev)
+              h <- fromIntegral <$> c_rt_image_height cam
+              let w = R.cs_imageWidth settings
+              if h <= 0 || w <= 0 then pure (Left (LibraryError (-2) "empty image")) else
+                alloca $ \pscene -> alloca $ \pfilm -> do
+                  rc0 <- c_rt_scene_create sc (fromIntegral dev) pscene
+                  if rc0 /= 0 then libraryError rc0 else do
+                    scene <- peek pscene
+                    rc1 <- c_rt_film_create scene cam (philoxKey gen) ex pfilm
+                    r <- if rc1 /= 0 then libraryError rc1 else do
+                      film <- peek pfilm
+                      done <- filmPasses film (R.cs_samplesPerPixel settings) target (max 1 batch)
+                      out <- case done of
+                        Left e -> pure (Left e)
+                        Right spp -> fmap (\img -> (img, spp)) <$> filmImage (doPrecision opts) film h w
+                      _ <- c_rt_film_destroy film
+                      pure out
+                    _ <- c_rt_scene_destroy scene
+                    pure r
+    _ -> pure (Left NotReifiable)
+
+-- | Add passes of @batch@ samples to a film until its noise figure is at most @target@ (from the
+-- second pass on) or it holds @maxSpp@ samples; the samples per pixel it then holds.
+filmPasses :: Ptr () -> Int -> Double -> Int -> IO (Either RenderError Int)
+filmPasses film maxSpp target batch = alloca $ \pnoise -> go pnoise 0 (0 :: Int)
+  where
+    go :: Ptr CDouble -> Int -> Int -> IO (Either RenderError Int)
+    go pnoise spp passes
+      | spp >= maxSpp = pure (Right spp)
+      | otherwise = do
+          let n = min batch (maxSpp - spp)
+          rc <- c_rt_film_add film (fromIntegral n) nullPtr
+          if rc /= 0 then libraryError rc
+            else if passes + 1 < 2 then go pnoise (spp + n) (passes + 1)
+            else do
+              rcn <- c_rt_film_noise film nullPtr pnoise
+              if rcn /= 0 then libraryError rcn else do
+                figure <- peek pnoise
+                if (realToFrac figure :: Double) <= target then pure (Right (spp + n))
+                  else go pnoise (spp + n) (passes + 1)
+
+-- | The film's image (rt_film_read) as a storable matrix; FP32 films are widened to Double.
+filmImage :: Precision -> Ptr () -> Int -> Int -> IO (Either RenderError (A.Matrix A.S Color))
+filmImage prec film h w = do
+  let n = 3 * h * w
+      asColors fp = A.resize' (A.Sz2 h w) (AU.unsafeArrayFromForeignPtr0 A.Par (fp :: ForeignPtr Color) (A.Sz1 (h * w)))
+  fp <- mallocForeignPtrArray n :: IO (ForeignPtr CDouble)
+  if prec == Binary64
+    then do
+      rc <- withForeignPtr fp $ \out -> c_rt_film_read film (castPtr out)
+      if rc /= 0 then libraryError rc else pure (Right (asColors (castForeignPtr fp)))
+    else do
+      fp32 <- mallocForeignPtrArray n :: IO (ForeignPtr CFloat)
+      rc <- withForeignPtr fp32 $ \out -> c_rt_film_read film (castPtr out)
+      if rc /= 0 then libraryError rc else do
+        withForeignPtr fp32 $ \src -> withForeignPtr fp $ \dst ->
+          forM_ [0 .. n - 1] $ \i -> peekElemOff src i >>= pokeElemOff dst i . realToFrac
+        pure (Right (asColors (castForeignPtr fp)))
+
+-- | 'raytrace' that stops when the image is clean enough: @raytraceUntil settings world gen noise
+-- batch@ renders passes of @batch@ samples until the frame's relative noise figure is at most
+-- @noise@ or cs_samplesPerPixel samples per pixel are reached, and returns the image with its
+-- samples per pixel.  The fallback rules are 'raytrace''s; the CPU path has no film and renders
+-- all cs_samplesPerPixel samples.
+raytraceUntil :: R.ToRandom m => R.CameraSettings -> Geometry m Material -> StdGen -> Double -> Int
+              -> (A.Matrix A.D Color, Int)
+raytraceUntil settings world gen noise batch =
+  case unsafePerformIO (renderUntilOnDevice defaultDeviceOptions settings world gen noise batch) of
+    Right (img, spp) -> (A.delay img, spp)
+    Left e | fallback e -> (R.raytrace settings (toReferenceRandom world) gen, R.cs_samplesPerPixel settings)
+           | otherwise -> error ("Graphics.Ray.Device.raytraceUntil: the film failed: " ++ show e)
+{-# NOINLINE raytraceUntil #-}

@@ -309,6 +309,58 @@ int rt_multi_render(const rt_multi_scene* m, const rt_camera_settings* cs, uint6
 int rt_encode8_async(const void* d_rgb, int32_t in_f64, uint8_t* d_out, int64_t n_values, int32_t encoding,
                      void* hip_stream);
 
+/* Progressive film: the device-resident accumulation state of one (scene, camera, seed, precision,
+ * shard).  Samples are added in passes, and the film can be resolved to an image, asked for a noise
+ * estimate, saved and loaded at any time.  The sample index is a word of the Philox counter and the
+ * per-pixel sums are integers, so passes of a, b, c, ... samples give the image of ONE render of
+ * a + b + c + ... samples, bit for bit (rt_render / rt_render_async with that samples_per_pixel).
+ *
+ * rt_film_create: `s` is the film's scene and must outlive it; ex as for rt_render_async (n_devices
+ *   0, no RT_EXEC_ENCODE8_* bit; a shard is allowed: the film then holds that shard's tile).
+ *   cs->samples_per_pixel is validated and then not read: the film's count is what has been added.
+ *   Every device buffer is allocated here (the first film of a precision also uploads the scene's
+ *   records of that precision): rt_film_add allocates nothing.  A pass runs alone on its stream
+ *   (its merge follows it), so passes are planned as RT_EXEC_SOLO renders whatever ex->flags says.
+ * rt_film_add: enqueue samples [N, N + n_samples) of every pixel and their merge on hip_stream;
+ *   n_samples <= 0 or a total beyond 2^24 samples is RT_E_INVALID.  Asynchronous.  A film's calls
+ *   are ordered by the caller: one stream, or events between streams.
+ * rt_film_resolve: enqueue the mean of the samples so far into d_out_rgb (a device buffer as
+ *   rt_render_async's: rt_shard_rows(h, ex) * width * 3 doubles, floats with RT_EXEC_F32).
+ * The synchronous calls (read, noise, get_info, save, load, reset) run behind the stream of the
+ *   last rt_film_add and wait for it.  rt_film_read: the resolved tile in a host buffer; RT_E_STACK
+ *   (image written) when the scene's traversal-stack word is set.
+ * rt_film_noise: the relative standard error of each pixel's mean R + G + B, estimated from the
+ *   passes (batch means; any pass sizes; needs two passes, else RT_E_INVALID), against
+ *   max(mean, 3 / 256); *noise = sqrt(mean of its square) over the pixels that count (not NaN-
+ *   flagged, not a shard's padding row; those are NaN in the map), identical from run to run.
+ *   d_map_or_null: a device buffer of one float per tile pixel, or NULL.
+ * rt_film_save / rt_film_load: the state (rt_film_state_bytes: a 64-byte header — magic, layout
+ *   version, precision, width, height, tile rows, shard triple, Philox key, samples, passes — then
+ *   the sums, the NaN flags and the estimator's word per pixel) to / from a host buffer.  Load
+ *   rejects a state whose header does not match the film it is loaded into (RT_E_INVALID).  The
+ *   header does NOT identify the scene or the camera's position: loading a state into a film of
+ *   the scene and camera it was saved from is the caller's responsibility. */
+typedef struct rt_film rt_film;
+typedef struct rt_film_info {
+  int64_t samples;       /* per pixel, all passes */
+  int32_t passes;
+  int32_t width, rows;   /* the tile: rt_shard_rows(h, ex) rows */
+  int32_t nan_pixels;    /* pixels with a non-finite sample so far (NaN in the image) */
+  int32_t f32;           /* 1: RT_EXEC_F32 */
+} rt_film_info;
+int rt_film_create(const rt_device_scene* s, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex,
+                   rt_film** out);
+int rt_film_destroy(rt_film* f);
+int rt_film_reset(rt_film* f);   /* back to 0 samples */
+int rt_film_add(rt_film* f, int32_t n_samples, void* hip_stream);
+int rt_film_resolve(const rt_film* f, void* d_out_rgb, void* hip_stream);
+int rt_film_read(const rt_film* f, void* host_out_rgb);
+int rt_film_noise(const rt_film* f, float* d_map_or_null, double* noise);
+int rt_film_get_info(const rt_film* f, rt_film_info* info);
+int rt_film_state_bytes(const rt_film* f, int64_t* bytes);
+int rt_film_save(const rt_film* f, void* host_buf, int64_t cap);
+int rt_film_load(rt_film* f, const void* host_buf, int64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,9 @@ RT_OK, RT_E_GENERIC, RT_E_INVALID, RT_E_UNSUPPORTED, RT_E_HIP, RT_E_STACK = 0, -
 
 EXPORTED = ["rt_abi_version", "rt_last_error", "rt_device_count", "rt_image_height", "rt_shard_rows", "rt_shard_row", "rt_render",
             "rt_scene_create", "rt_scene_destroy", "rt_scene_stats", "rt_render_async", "rt_encode8_async",
-            "rt_multi_scene_create", "rt_multi_scene_destroy", "rt_multi_render"]
+            "rt_multi_scene_create", "rt_multi_scene_destroy", "rt_multi_render",
+            "rt_film_create", "rt_film_destroy", "rt_film_reset", "rt_film_add", "rt_film_resolve", "rt_film_read",
+            "rt_film_noise", "rt_film_get_info", "rt_film_state_bytes", "rt_film_save", "rt_film_load"]
 
 
 class RtRedirectTarget(ctypes.Structure):
@@ -75,6 +77,11 @@ class RtStats(ctypes.Structure):
                 ("device_allocs", ctypes.c_int32), ("kernel_block", ctypes.c_int32)]
 
 
+class RtFilmInfo(ctypes.Structure):
+    _fields_ = [("samples", ctypes.c_int64), ("passes", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("rows", ctypes.c_int32), ("nan_pixels", ctypes.c_int32), ("f32", ctypes.c_int32)]
+
+
 _lib = None
 
 
@@ -108,6 +115,18 @@ def load():
     L.rt_multi_scene_destroy.argtypes = [P]
     L.rt_multi_render.argtypes = [P, ctypes.POINTER(RtCameraSettings), ctypes.c_uint64, ctypes.POINTER(RtExec), P,
                                   ctypes.POINTER(RtStats)]
+    L.rt_film_create.argtypes = [P, ctypes.POINTER(RtCameraSettings), ctypes.c_uint64, ctypes.POINTER(RtExec),
+                                 ctypes.POINTER(ctypes.c_void_p)]
+    L.rt_film_destroy.argtypes = [P]
+    L.rt_film_reset.argtypes = [P]
+    L.rt_film_add.argtypes = [P, ctypes.c_int32, P]
+    L.rt_film_resolve.argtypes = [P, P, P]
+    L.rt_film_read.argtypes = [P, P]
+    L.rt_film_noise.argtypes = [P, P, ctypes.POINTER(ctypes.c_double)]
+    L.rt_film_get_info.argtypes = [P, ctypes.POINTER(RtFilmInfo)]
+    L.rt_film_state_bytes.argtypes = [P, ctypes.POINTER(ctypes.c_int64)]
+    L.rt_film_save.argtypes = [P, P, ctypes.c_int64]
+    L.rt_film_load.argtypes = [P, P, ctypes.c_int64]
     for name in EXPORTED:
         getattr(L, name)
     if L.rt_abi_version() != ABI_VERSION:

@@ -3,7 +3,7 @@
 // kernel launch (rt_kernel.hip / rt_kernel64.hip), multi-device scenes (one process, many GPUs:
 // concurrent uploads, shard renders on per-device streams, a device-side gather by peer copies
 // into the first device's framebuffer and ONE device-to-host copy), the 8-bit output epilogue,
-// error reporting.
+// the progressive film (its state and entry points; kernels in rt_film.hip), error reporting.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/rt.h"
+#include "rt_film.h"
 #include "rt_internal.h"
 #include "rt_kernel_class.h"
 
@@ -155,6 +156,45 @@ struct rt_multi_scene {
   int* h_status = nullptr;                 // pinned host word: the one-device render's status read-back
 };
 
+// A progressive film (include/rt.h rt_film_*, rt_film.h): the device-resident accumulation state of
+// one (scene, camera, seed, precision, shard).  One device allocation made at create holds the
+// totals, flags and q, the pass workspace a render writes, the resolved tile of rt_film_read and
+// the noise figure's partials: rt_film_add allocates nothing.
+struct FilmHeader {  // the saved state's header (rt_film_save); totals, flags and q follow
+  uint32_t magic, version;
+  int32_t f32, width, height, rows, n_shards, shard, row_block, passes;
+  uint32_t key0, key1;
+  int64_t samples;
+  int64_t reserved;
+};
+static_assert(sizeof(FilmHeader) == 64, "the saved film header is 64 bytes");
+constexpr uint32_t kFilmMagic = 0x4d4c4652u;  // "RFLM"
+constexpr uint32_t kFilmVersion = 1;
+struct rt_film {
+  const rt_device_scene* scene = nullptr;
+  rt_camera_settings cs{};
+  std::vector<rt_redirect_target> targets;  // cs.redirect_targets points here
+  uint64_t seed = 0;
+  rt_exec ex{};
+  bool f32 = false;
+  int width = 0, height = 0, rows = 0, acc_words = 0;
+  size_t n_pixels = 0;
+  int64_t samples = 0;  // N
+  int32_t passes = 0;   // K
+  char* mem = nullptr;  // the one allocation; the parts below point into it
+  unsigned long long* total = nullptr;
+  unsigned int* flags = nullptr;
+  double* q = nullptr;
+  char* ws = nullptr;
+  size_t ws_bytes = 0;
+  void* tile = nullptr;
+  double* partial_sum = nullptr;
+  int* partial_cnt = nullptr;
+  size_t total_bytes = 0, flag_bytes = 0, q_bytes = 0, state_span = 0;  // (padded; total, flags, q are contiguous)
+  hipStream_t last = nullptr;  // the stream of the last enqueue: the synchronous calls run behind it
+  std::mutex mu;
+};
+
 namespace {
 
 // one render of the scene's records of precision R, enqueued on `stream`
@@ -202,7 +242,9 @@ int ensure_precision(const rt_device_scene* s) {
 
 // the stream-ordered workspace of one render: fixed-point sums, NaN flags, queue head words
 size_t workspace_bytes(size_t tile_pixels, int acc_words, size_t* off_flag, size_t* off_ctr) {
-  const size_t of = tile_pixels * acc_words * sizeof(long long);
+  // (every part 256-byte aligned, zeroed slack behind the sums and the flags: rt_film.hip reads
+  // both as 16-byte vectors)
+  const size_t of = (tile_pixels * acc_words * sizeof(long long) + 255) & ~(size_t)255;
   const size_t oc = of + ((tile_pixels * sizeof(unsigned) + 255) & ~(size_t)255);
   if (off_flag) *off_flag = of;
   if (off_ctr) *off_ctr = oc;
@@ -217,9 +259,12 @@ size_t workspace_bytes(size_t tile_pixels, int acc_words, size_t* off_flag, size
 // (one binary64 Cornell launch 5.385 -> 5.164 ms; with frames overlapped on two streams, as
 // rt_render_async callers run them, 128 is as fast and the README scene 2 % faster:
 // profiles/r5/pool).  Env RT_AMD_POOL_SHIFT overrides (experiments).
+// sample0 / resolve: a film pass (rt_film_add) renders samples [sample0, sample0 + spp) and leaves
+// the sums in the workspace (no mean: d_out is unused) for rt_film_merge_kernel.
 template <class R>
 int render_async(const rt_device_scene* s, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex, R* d_out,
-                 void* hip_stream, char* ws_given = nullptr, size_t ws_cap = 0, int frame_rows = 0, bool lone = false) {
+                 void* hip_stream, char* ws_given = nullptr, size_t ws_cap = 0, int frame_rows = 0, bool lone = false,
+                 int sample0 = 0, bool resolve = true) {
   if (int rc = ensure_precision<R>(s)) return rc;
   lone = lone || (ex && (ex->flags & RT_EXEC_SOLO));  // (the caller says this render runs alone)
   const DevArrays<R>& A = s->arrays<R>();
@@ -259,6 +304,7 @@ int render_async(const rt_device_scene* s, const rt_camera_settings* cs, uint64_
   rt_host_plan_work(P, (long long)A.resident_blocks * rt_class_block(sizeof(R) == 8, c), c.var == RT_VAR_FLAT, lone);
   P.trav_exit_pct = sizeof(R) == 8 ? s->trav_exit_pct64 : s->trav_exit_pct;
   P.out_frame_rows = frame_rows;
+  P.sample0 = sample0;
   HIP_TRY(hipSetDevice(s->device));
   // stream-ordered workspace: fixed-point sums, NaN flags, queue counter (graph-capturable)
   const size_t tile_pixels = (size_t)P.tile_rows * P.cam.width;
@@ -279,7 +325,8 @@ int render_async(const rt_device_scene* s, const rt_camera_settings* cs, uint64_
   // frame's grid; binary64's runs in 23 us either way (its kernel leaves VGPRs free) — so 0.
   int reserve = A.resident_blocks > 16 * RT_GRID_RESERVE ? RT_GRID_RESERVE : 0;
   if (const char* e = rt_knob("RT_AMD_GRID_RESERVE")) reserve = std::max(0, std::min(A.resident_blocks - 1, atoi(e)));
-  if (rt_launch_render(P, A.resident_blocks - reserve, s->variant, hip_stream) || rt_launch_resolve(P, hip_stream))
+  if (rt_launch_render(P, A.resident_blocks - reserve, s->variant, hip_stream) ||
+      (resolve && rt_launch_resolve(P, hip_stream)))
     rc = fail(RT_E_HIP, "kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
   if (own) HIP_TRY(hipFreeAsync(ws, st));
   return rc;
@@ -720,6 +767,59 @@ int build_host(const rt_scene* sc, std::shared_ptr<const HostScene>& out, double
   return RT_OK;
 }
 
+// ---- progressive film (rt_film.h)
+
+FilmHeader film_header(const rt_film* f) {
+  FilmHeader h{};
+  h.magic = kFilmMagic;
+  h.version = kFilmVersion;
+  h.f32 = f->f32;
+  h.width = f->width;
+  h.height = f->height;
+  h.rows = f->rows;
+  h.n_shards = f->ex.n_shards;
+  h.shard = f->ex.shard;
+  h.row_block = f->ex.row_block;
+  h.passes = f->passes;
+  h.key0 = (uint32_t)f->seed;  // the Philox key (rt_build.cpp rt_host_make_params)
+  h.key1 = (uint32_t)(f->seed >> 32);
+  h.samples = f->samples;
+  return h;
+}
+// the saved state: header, totals, flags, q (unpadded)
+size_t film_sums_bytes(const rt_film* f) { return f->n_pixels * f->acc_words * sizeof(long long); }
+int64_t film_state_bytes(const rt_film* f) {
+  return (int64_t)(sizeof(FilmHeader) + film_sums_bytes(f) + f->n_pixels * (sizeof(unsigned) + sizeof(double)));
+}
+void film_destroy(rt_film* f) {
+  if (!f) return;
+  if (f->mem) {
+    (void)hipSetDevice(f->scene->device);
+    if (f->last) (void)hipStreamSynchronize(f->last);
+    (void)hipFree(f->mem);
+  }
+  delete f;
+}
+// the film's totals as one-shot kernel parameters of N samples: what rt_resolve_kernel reads
+template <class R>
+int film_resolve(const rt_film* f, void* d_out, hipStream_t st) {
+  KernelParamsT<R> P;
+  std::memset(&P, 0, sizeof P);
+  rt_camera_settings cs = f->cs;
+  cs.samples_per_pixel = (int32_t)f->samples;
+  std::string err;
+  if (int rc = rt_host_make_params(&cs, f->seed, &f->ex, P, err)) return fail(rc, "%s", err.c_str());
+  P.accum = f->total;
+  P.nanflag = f->flags;
+  P.out = (R*)d_out;
+  if (rt_launch_resolve(P, st)) return fail(RT_E_HIP, "resolve launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return RT_OK;
+}
+int film_resolve_any(const rt_film* f, void* d_out, hipStream_t st) {
+  if (f->samples <= 0) return fail(RT_E_INVALID, "the film holds no samples");
+  HIP_TRY(hipSetDevice(f->scene->device));
+  return f->f32 ? film_resolve<float>(f, d_out, st) : film_resolve<double>(f, d_out, st);
+}
 
 }  // namespace
 
@@ -854,6 +954,220 @@ int rt_encode8_async(const void* d_rgb, int32_t in_f64, uint8_t* d_out, int64_t 
   if (encoding != 0 && encoding != 1) return fail(RT_E_INVALID, "encoding must be 0 (sRGB) or 1 (sqrt)");
   if (rt_launch_encode8(d_rgb, in_f64 ? 1 : 0, d_out, n_values, encode8_table(encoding), encoding, hip_stream))
     return fail(RT_E_HIP, "encode launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return RT_OK;
+}
+
+// ---- progressive film
+
+int rt_film_create(const rt_device_scene* s, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex,
+                   rt_film** out) {
+  if (!s || !cs || !ex || !out) return fail(RT_E_INVALID, "null argument");
+  *out = nullptr;
+  if (ex->n_devices != 0) return fail(RT_E_INVALID, "a film lives on the scene's device (n_devices = 0)");
+  if (int rc = check_flags(ex)) return rc;
+  if (exec_encoding(ex) >= 0) return fail(RT_E_INVALID, "a film resolves to linear RGB (use rt_encode8_async)");
+  if (cs->n_redirect_targets < 0 || cs->n_redirect_targets > RT_MAX_TARGETS || (cs->n_redirect_targets && !cs->redirect_targets))
+    return fail(cs->n_redirect_targets > RT_MAX_TARGETS ? RT_E_UNSUPPORTED : RT_E_INVALID, "invalid redirect targets (%d)",
+                cs->n_redirect_targets);
+  const int h = rt_host_image_height(cs);
+  if (h <= 0 || cs->image_width <= 0) return fail(RT_E_INVALID, "image %dx%d must be non-empty", cs->image_width, h);
+  {  // validate the camera (samples_per_pixel included; it is not read afterwards) before the device
+    KernelParams P;
+    std::string err;
+    if (int rc = rt_host_make_params(cs, seed, ex, P, err)) return fail(rc, "%s", err.c_str());
+  }
+  std::unique_ptr<rt_film, void (*)(rt_film*)> f(new rt_film(), film_destroy);
+  f->scene = s;
+  f->cs = *cs;
+  f->targets.assign(cs->redirect_targets, cs->redirect_targets + cs->n_redirect_targets);
+  f->cs.redirect_targets = f->targets.empty() ? nullptr : f->targets.data();
+  f->seed = seed;
+  f->ex = *ex;
+  f->ex.flags |= RT_EXEC_SOLO;  // a pass is followed by its merge on the same stream: it runs alone
+  f->ex.devices = nullptr;
+  f->f32 = exec_f32(ex);
+  f->width = cs->image_width;
+  f->height = h;
+  f->rows = rt_host_shard_rows(h, ex);
+  f->acc_words = f->f32 ? RT_ACC_WORDS(float) : RT_ACC_WORDS(double);
+  f->n_pixels = (size_t)f->rows * f->width;
+  if (int rc = ensure_precisions(s, f->f32 ? 1 : 2)) return rc;
+  auto pad = [](size_t b) { return (b + 16 + 255) & ~(size_t)255; };  // >= 16 bytes of slack, 256-byte parts
+  f->total_bytes = pad(film_sums_bytes(f.get()));
+  f->flag_bytes = pad(f->n_pixels * sizeof(unsigned));
+  f->q_bytes = pad(f->n_pixels * sizeof(double));
+  f->state_span = f->total_bytes + f->flag_bytes + f->q_bytes;
+  f->ws_bytes = workspace_bytes(f->n_pixels, f->acc_words, nullptr, nullptr);
+  const size_t tile_bytes = pad(f->n_pixels * 3 * (f->f32 ? sizeof(float) : sizeof(double)));
+  const size_t blocks = (size_t)rt_film_blocks((long long)f->n_pixels);
+  const size_t part_bytes = pad(blocks * sizeof(double)) + pad(blocks * sizeof(int));
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipMalloc((void**)&f->mem, f->state_span + f->ws_bytes + tile_bytes + part_bytes));
+  char* p = f->mem;
+  f->total = (unsigned long long*)p, p += f->total_bytes;
+  f->flags = (unsigned int*)p, p += f->flag_bytes;
+  f->q = (double*)p, p += f->q_bytes;
+  f->ws = p, p += f->ws_bytes;
+  f->tile = p, p += tile_bytes;
+  f->partial_sum = (double*)p, p += pad(blocks * sizeof(double));
+  f->partial_cnt = (int*)p;
+  HIP_TRY(hipMemset(f->mem, 0, f->state_span));
+  *out = f.release();
+  return RT_OK;
+}
+
+int rt_film_destroy(rt_film* f) {
+  film_destroy(f);
+  return RT_OK;
+}
+
+int rt_film_reset(rt_film* f) {
+  if (!f) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(f->mu);
+  HIP_TRY(hipSetDevice(f->scene->device));
+  HIP_TRY(hipMemsetAsync(f->mem, 0, f->state_span, f->last));
+  HIP_TRY(hipStreamSynchronize(f->last));
+  f->samples = 0;
+  f->passes = 0;
+  return RT_OK;
+}
+
+int rt_film_add(rt_film* f, int32_t n_samples, void* hip_stream) {
+  if (!f) return fail(RT_E_INVALID, "null argument");
+  if (n_samples <= 0) return fail(RT_E_INVALID, "a pass adds at least one sample (%d)", n_samples);
+  std::lock_guard<std::mutex> lock(f->mu);
+  if (f->samples + n_samples > RT_FILM_MAX_SAMPLES)
+    return fail(RT_E_INVALID, "a film holds at most 2^24 samples per pixel (%lld + %d)", (long long)f->samples, n_samples);
+  rt_camera_settings cs = f->cs;
+  cs.samples_per_pixel = n_samples;
+  const int s0 = (int)f->samples;
+  const int rc = f->f32 ? render_async<float>(f->scene, &cs, f->seed, &f->ex, (float*)nullptr, hip_stream, f->ws,
+                                              f->ws_bytes, 0, true, s0, false)
+                        : render_async<double>(f->scene, &cs, f->seed, &f->ex, (double*)nullptr, hip_stream, f->ws,
+                                               f->ws_bytes, 0, true, s0, false);
+  if (rc) return rc;
+  f->last = (hipStream_t)hip_stream;
+  size_t off_flag = 0;
+  (void)workspace_bytes(f->n_pixels, f->acc_words, &off_flag, nullptr);
+  if (rt_film_launch_merge(f->total, f->flags, f->q, (const unsigned long long*)f->ws,
+                           (const unsigned int*)(f->ws + off_flag), (long long)f->n_pixels, f->acc_words, n_samples,
+                           hip_stream))
+    return fail(RT_E_HIP, "merge launch failed: %s", hipGetErrorString(hipGetLastError()));
+  f->samples += n_samples;
+  f->passes += 1;
+  return RT_OK;
+}
+
+int rt_film_resolve(const rt_film* f, void* d_out_rgb, void* hip_stream) {
+  if (!f || !d_out_rgb) return fail(RT_E_INVALID, "null argument");
+  return film_resolve_any(f, d_out_rgb, (hipStream_t)hip_stream);
+}
+
+int rt_film_read(const rt_film* f, void* host_out_rgb) {
+  if (!f || !host_out_rgb) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(const_cast<rt_film*>(f)->mu);  // (the tile is the film's scratch)
+  if (int rc = film_resolve_any(f, f->tile, f->last)) return rc;
+  const size_t bytes = f->n_pixels * 3 * (f->f32 ? sizeof(float) : sizeof(double));
+  int status = 0;
+  HIP_TRY(hipMemcpyAsync(host_out_rgb, f->tile, bytes, hipMemcpyDeviceToHost, f->last));
+  HIP_TRY(hipMemcpyAsync(&status, f->scene->status, sizeof(int), hipMemcpyDeviceToHost, f->last));
+  HIP_TRY(hipStreamSynchronize(f->last));
+  if (status) return fail(RT_E_STACK, "BVH traversal stack overflow");
+  return RT_OK;
+}
+
+int rt_film_noise(const rt_film* f, float* d_map_or_null, double* noise) {
+  if (!f || !noise) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(const_cast<rt_film*>(f)->mu);  // (the partials are the film's scratch)
+  if (f->passes < 2) return fail(RT_E_INVALID, "a noise estimate needs two passes (the film has %d)", f->passes);
+  HIP_TRY(hipSetDevice(f->scene->device));
+  if (rt_film_launch_noise(f->total, f->flags, f->q, d_map_or_null, f->partial_sum, f->partial_cnt,
+                           (long long)f->n_pixels, f->acc_words, f->samples, f->passes, f->width, f->height,
+                           f->ex.n_shards, f->ex.shard, f->ex.row_block, f->last))
+    return fail(RT_E_HIP, "noise launch failed: %s", hipGetErrorString(hipGetLastError()));
+  const size_t blocks = (size_t)rt_film_blocks((long long)f->n_pixels);
+  std::vector<double> ps(blocks);
+  std::vector<int> pc(blocks);
+  HIP_TRY(hipMemcpyAsync(ps.data(), f->partial_sum, blocks * sizeof(double), hipMemcpyDeviceToHost, f->last));
+  HIP_TRY(hipMemcpyAsync(pc.data(), f->partial_cnt, blocks * sizeof(int), hipMemcpyDeviceToHost, f->last));
+  HIP_TRY(hipStreamSynchronize(f->last));
+  double sum = 0.0;  // the workgroups' partials in index order: the same figure on every run
+  long long cnt = 0;
+  for (size_t b = 0; b < blocks; ++b) sum += ps[b], cnt += pc[b];
+  *noise = cnt > 0 ? std::sqrt(sum / (double)cnt) : std::nan("");
+  return RT_OK;
+}
+
+int rt_film_get_info(const rt_film* f, rt_film_info* info) {
+  if (!f || !info) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(const_cast<rt_film*>(f)->mu);
+  std::vector<unsigned> flags(f->n_pixels);
+  HIP_TRY(hipSetDevice(f->scene->device));
+  HIP_TRY(hipMemcpyAsync(flags.data(), f->flags, f->n_pixels * sizeof(unsigned), hipMemcpyDeviceToHost, f->last));
+  HIP_TRY(hipStreamSynchronize(f->last));
+  info->samples = f->samples;
+  info->passes = f->passes;
+  info->width = f->width;
+  info->rows = f->rows;
+  info->nan_pixels = (int32_t)std::count_if(flags.begin(), flags.end(), [](unsigned v) { return v != 0u; });
+  info->f32 = f->f32;
+  return RT_OK;
+}
+
+int rt_film_state_bytes(const rt_film* f, int64_t* bytes) {
+  if (!f || !bytes) return fail(RT_E_INVALID, "null argument");
+  *bytes = film_state_bytes(f);
+  return RT_OK;
+}
+
+int rt_film_save(const rt_film* f, void* host_buf, int64_t cap) {
+  if (!f || !host_buf) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(const_cast<rt_film*>(f)->mu);
+  if (cap < film_state_bytes(f))
+    return fail(RT_E_INVALID, "the film's state takes %lld bytes (buffer: %lld)", (long long)film_state_bytes(f), (long long)cap);
+  const FilmHeader h = film_header(f);
+  char* p = (char*)host_buf;
+  std::memcpy(p, &h, sizeof h), p += sizeof h;
+  HIP_TRY(hipSetDevice(f->scene->device));
+  HIP_TRY(hipMemcpyAsync(p, f->total, film_sums_bytes(f), hipMemcpyDeviceToHost, f->last));
+  p += film_sums_bytes(f);
+  HIP_TRY(hipMemcpyAsync(p, f->flags, f->n_pixels * sizeof(unsigned), hipMemcpyDeviceToHost, f->last));
+  p += f->n_pixels * sizeof(unsigned);
+  HIP_TRY(hipMemcpyAsync(p, f->q, f->n_pixels * sizeof(double), hipMemcpyDeviceToHost, f->last));
+  HIP_TRY(hipStreamSynchronize(f->last));
+  return RT_OK;
+}
+
+int rt_film_load(rt_film* f, const void* host_buf, int64_t bytes) {
+  if (!f || !host_buf) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(f->mu);
+  if (bytes < (int64_t)sizeof(FilmHeader)) return fail(RT_E_INVALID, "not a saved film (%lld bytes)", (long long)bytes);
+  FilmHeader h;
+  std::memcpy(&h, host_buf, sizeof h);
+  if (h.magic != kFilmMagic || h.version != kFilmVersion)
+    return fail(RT_E_INVALID, "not a saved film of layout version %u", kFilmVersion);
+  const FilmHeader w = film_header(f);
+  if (h.f32 != w.f32 || h.width != w.width || h.height != w.height || h.rows != w.rows || h.n_shards != w.n_shards ||
+      h.shard != w.shard || h.row_block != w.row_block || h.key0 != w.key0 || h.key1 != w.key1)
+    return fail(RT_E_INVALID,
+                "the saved film (%s, %dx%d, shard %d of %d by %d rows, key %08x%08x) does not match this film (%s, "
+                "%dx%d, shard %d of %d by %d rows, key %08x%08x)",
+                h.f32 ? "f32" : "f64", h.width, h.height, h.shard, h.n_shards, h.row_block, h.key1, h.key0,
+                w.f32 ? "f32" : "f64", w.width, w.height, w.shard, w.n_shards, w.row_block, w.key1, w.key0);
+  if (bytes != film_state_bytes(f) || h.samples < 0 || h.samples > RT_FILM_MAX_SAMPLES || h.passes < 0 ||
+      h.passes > h.samples)
+    return fail(RT_E_INVALID, "the saved film is damaged (%lld bytes, %lld samples, %d passes)", (long long)bytes,
+                (long long)h.samples, h.passes);
+  const char* p = (const char*)host_buf + sizeof h;
+  HIP_TRY(hipSetDevice(f->scene->device));
+  HIP_TRY(hipMemcpyAsync(f->total, p, film_sums_bytes(f), hipMemcpyHostToDevice, f->last));
+  p += film_sums_bytes(f);
+  HIP_TRY(hipMemcpyAsync(f->flags, p, f->n_pixels * sizeof(unsigned), hipMemcpyHostToDevice, f->last));
+  p += f->n_pixels * sizeof(unsigned);
+  HIP_TRY(hipMemcpyAsync(f->q, p, f->n_pixels * sizeof(double), hipMemcpyHostToDevice, f->last));
+  HIP_TRY(hipStreamSynchronize(f->last));
+  f->samples = h.samples;
+  f->passes = h.passes;
   return RT_OK;
 }
 

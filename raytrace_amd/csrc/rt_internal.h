@@ -349,6 +349,10 @@ struct KernelParamsT {
   // global row, so no separate gather copy is needed (rt_api.hip multi_render)
   int out_frame_rows;
   FastDiv div_width, div_block;  // image width, row block
+  // first sample index of this launch: the items cover samples [sample0, sample0 + cam.spp) of
+  // every pixel (rt_trace.h open_item).  0 for a one-shot render; a film pass continues where the
+  // last one ended (rt_film.hip).  Last member: code that zero-fills the struct renders from 0
+  int sample0;
 };
 using DevMaterial = DevMaterialT<float>;
 using DevTexture = DevTextureT<float>;

@@ -1693,8 +1693,10 @@ RT_FN bool open_item(const KernelParams& P, int item, ItemCtx& I) {
   I.pxgy = (uint32_t)gy << 16 | (uint32_t)px;
   // big chunk k: samples [k big_chunk, (k + 1) big_chunk); small chunk k: from small_start + k chunk
   const int chunk = big ? P.big_chunk : P.chunk;
-  I.sample = (big || !kTwoSizes ? 0 : P.small_start) + k * chunk;
-  I.s_end = I.sample + chunk < P.cam.spp ? I.sample + chunk : P.cam.spp;
+  // (all shifted by the launch's first sample: a film pass renders [sample0, sample0 + spp))
+  I.sample = P.sample0 + (big || !kTwoSizes ? 0 : P.small_start) + k * chunk;
+  const int last = P.sample0 + P.cam.spp;
+  I.s_end = I.sample + chunk < last ? I.sample + chunk : last;
   if (gy >= P.cam.height || P.cam.max_depth <= 0) I.s_end = I.sample;  // padding row / black image
   return I.sample < I.s_end;
 }

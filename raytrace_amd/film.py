@@ -1,0 +1,215 @@
+"""Progressive rendering: a `Film` keeps a frame's accumulation state on the GPU (include/rt.h
+rt_film_*), so samples can be added to it in passes, the image read at any time, the noise
+estimated and the state saved and restored.
+
+The sample index is a word of the Philox counter and the per-pixel sums are integers, so passes
+of a, b, c samples give exactly the image of `raytrace` at a + b + c samples per pixel.
+
+    film = Film(world, settings, seed)
+    film.add(8); preview = film.image()
+    while film.passes < 2 or film.noise() > 0.02:
+        film.add(16)
+    state = film.state()            # a numpy uint8 array: np.save it, film.restore it later
+
+`raytrace_until` is that loop as one call.  `noise_from_sums` restates the estimator in numpy.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import numpy as np
+
+from . import _lib
+from .camera import CameraSettings
+from .ray import DeviceScene, _seed64
+
+MAX_SAMPLES = 1 << 24  # per pixel and film (rt_film.h RT_FILM_MAX_SAMPLES)
+FLOOR = 3.0 / 256.0    # one 8-bit code per channel: below it a relative error cannot be shown
+
+
+class Film:
+    """The resident accumulation state of one (scene, camera, seed, precision, shard) on one GPU.
+
+    `world`: a scene description (uploaded here, freed by close()) or a DeviceScene (the caller's:
+    it must outlive the film).  `settings.cs_samplesPerPixel` is validated and otherwise ignored:
+    the film's sample count `.spp` is what has been added in `.passes` passes.  With n_shards > 1
+    the film holds that shard's tile (rt_exec row interleave; `render_shard`'s rows)."""
+
+    def __init__(self, world, settings: CameraSettings, seed, precision: str = "f64", device: int = 0,
+                 n_shards: int = 1, shard: int = 0, row_block: int = 4):
+        self._lib = _lib.load()
+        self.handle = None
+        self._own_scene = not isinstance(world, DeviceScene)
+        self.scene = DeviceScene(world, device) if self._own_scene else world
+        self.settings = settings
+        self.precision = precision
+        self.dtype = _lib.dtype_of(precision)
+        self._cs = _lib.camera_struct(settings)
+        self._ex = _lib.exec_struct(device=self.scene.device, n_shards=n_shards, shard=shard, row_block=row_block,
+                                    precision=precision)
+        h = ctypes.c_void_p()
+        try:
+            _lib.check(self._lib.rt_film_create(self.scene.handle, ctypes.byref(self._cs), _seed64(seed),
+                                                ctypes.byref(self._ex), ctypes.byref(h)))
+        except Exception:
+            if self._own_scene:
+                self.scene.close()
+            raise
+        self.handle = h
+        info = self.info()
+        self.shape = (info["rows"], info["width"], 3)
+
+    def info(self) -> dict:
+        st = _lib.RtFilmInfo()
+        _lib.check(self._lib.rt_film_get_info(self.handle, ctypes.byref(st)))
+        return dict(samples=st.samples, passes=st.passes, width=st.width, rows=st.rows, nan_pixels=st.nan_pixels,
+                    f32=bool(st.f32))
+
+    @property
+    def spp(self) -> int:
+        return self.info()["samples"]
+
+    @property
+    def passes(self) -> int:
+        return self.info()["passes"]
+
+    def add(self, n: int, stream_ptr: int = 0):
+        """Enqueue samples [spp, spp + n) of every pixel (asynchronous; returns self)."""
+        _lib.check(self._lib.rt_film_add(self.handle, int(n), ctypes.c_void_p(stream_ptr or None)))
+        return self
+
+    def image(self, out: np.ndarray | None = None) -> np.ndarray:
+        """The mean of the samples so far: (rows, width, 3) linear RGB, as `raytrace` at .spp."""
+        from .ray import _out_buffer
+        out = _out_buffer(out, self.shape, self.dtype)
+        _lib.check(self._lib.rt_film_read(self.handle, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def noise(self) -> float:
+        """sqrt(mean r^2) of the per-pixel relative standard error r (noise_map); needs two passes."""
+        v = ctypes.c_double()
+        _lib.check(self._lib.rt_film_noise(self.handle, None, ctypes.byref(v)))
+        return v.value
+
+    def noise_map(self) -> np.ndarray:
+        """(rows, width) float32: each pixel's relative standard error of its mean R + G + B against
+        max(mean, 3/256); NaN for pixels with a non-finite sample and a shard's padding rows."""
+        import torch
+        m = torch.empty(self.shape[0] * self.shape[1], dtype=torch.float32, device=f"cuda:{self.scene.device}")
+        v = ctypes.c_double()
+        _lib.check(self._lib.rt_film_noise(self.handle, ctypes.c_void_p(m.data_ptr()), ctypes.byref(v)))
+        return m.cpu().numpy().reshape(self.shape[:2])
+
+    def state(self) -> np.ndarray:
+        """The film's state as bytes (header, sums, flags, estimator words): see `unpack_state`."""
+        n = ctypes.c_int64()
+        _lib.check(self._lib.rt_film_state_bytes(self.handle, ctypes.byref(n)))
+        buf = np.zeros(n.value, np.uint8)
+        _lib.check(self._lib.rt_film_save(self.handle, buf.ctypes.data_as(ctypes.c_void_p), n.value))
+        return buf
+
+    def restore(self, state: np.ndarray):
+        """Load a state saved from a film of the same frame, seed, precision and shard (the header is
+        checked; that scene and camera are the same is the caller's responsibility)."""
+        buf = np.ascontiguousarray(state, np.uint8)
+        _lib.check(self._lib.rt_film_load(self.handle, buf.ctypes.data_as(ctypes.c_void_p), buf.size))
+        return self
+
+    def reset(self):
+        _lib.check(self._lib.rt_film_reset(self.handle))
+        return self
+
+    def close(self):
+        if self.handle:
+            self._lib.rt_film_destroy(self.handle)
+            self.handle = None
+            if self._own_scene:
+                self.scene.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+HEADER_DTYPE = np.dtype([("magic", "<u4"), ("version", "<u4"), ("f32", "<i4"), ("width", "<i4"), ("height", "<i4"),
+                         ("rows", "<i4"), ("n_shards", "<i4"), ("shard", "<i4"), ("row_block", "<i4"),
+                         ("passes", "<i4"), ("key0", "<u4"), ("key1", "<u4"), ("samples", "<i8"), ("reserved", "<i8")])
+
+
+def unpack_state(state: np.ndarray) -> dict:
+    """A saved state's parts: `header` (HEADER_DTYPE record), `sums` (rows, width, words) int64 — 3
+    words per pixel in FP32 (the RGB sums in units of 2^-32), 6 in binary64 (those, then the next
+    32 bits of each) —, `flags` (rows, width) uint32 and `q` (rows, width) float64."""
+    state = np.ascontiguousarray(state, np.uint8)
+    hd = state[:HEADER_DTYPE.itemsize].view(HEADER_DTYPE)[0]
+    rows, width, words = int(hd["rows"]), int(hd["width"]), 3 if hd["f32"] else 6
+    n = rows * width
+    o = HEADER_DTYPE.itemsize
+    sums = state[o:o + 8 * n * words].view("<i8").reshape(rows, width, words)
+    o += 8 * n * words
+    flags = state[o:o + 4 * n].view("<u4").reshape(rows, width)
+    o += 4 * n
+    q = state[o:o + 8 * n].view("<f8").reshape(rows, width)
+    return dict(header=hd, sums=sums, flags=flags, q=q)
+
+
+def noise_from_sums(pass_sums, pass_sizes) -> dict:
+    """The film's noise estimate from per-pass sums, in numpy (the operation sequence of rt_film.h).
+
+    pass_sums: integer array (K, ..., 3): per pass and pixel the RGB sums of that pass's samples in
+    the film's fixed-point unit 2^-32 (the first three words of `unpack_state(...)["sums"]`,
+    differenced between passes).  pass_sizes: the K sample counts.  Returns q, the per-sample
+    variance v (batch means: E[sum_k n_k (m_k - M)^2] = (K - 1) sigma^2 for any sizes) in squared
+    fixed-point units, the pixel mean M and its standard error se (both in radiance units), the
+    relative error r = se / max(M, 3/256) and the frame figure noise = sqrt(mean r^2)."""
+    sums = np.asarray(pass_sums, np.int64)
+    sizes = [int(n) for n in pass_sizes]
+    K = len(sizes)
+    if K < 2 or sums.shape[0] != K or sums.shape[-1] != 3 or min(sizes) <= 0:
+        raise ValueError("noise_from_sums needs K >= 2 passes of positive sizes and sums of shape (K, ..., 3)")
+    N = float(sum(sizes))
+    q = np.zeros(sums.shape[1:-1], np.float64)
+    for k in range(K):
+        L = sums[k].sum(-1, dtype=np.int64).astype(np.float64)
+        q = q + (L * L) / float(sizes[k])
+    T = sums.sum(0, dtype=np.int64).sum(-1, dtype=np.int64).astype(np.float64)
+    v = np.maximum(0.0, q - (T * T) / N) / float(K - 1)
+    se = np.sqrt(v / N) * 2.0 ** -32
+    M = T / N * 2.0 ** -32
+    r = se / np.maximum(M, FLOOR)
+    noise = math.sqrt(math.fsum((r * r).ravel().tolist()) / r.size) if r.size else float("nan")
+    return dict(q=q, v=v, se=se, mean=M, r=r, noise=noise)
+
+
+def raytrace_until(settings: CameraSettings, world, seed, noise: float, batch: int = 16, max_spp: int | None = None,
+                   **kw):
+    """Render in passes of `batch` samples until the frame's noise figure (Film.noise) is at most
+    `noise` (checked from the second pass on) or `max_spp` samples per pixel are reached (default
+    cs_samplesPerPixel; the last pass is cut to fit).  Returns (image, info): the image is
+    `raytrace`'s at info["spp"] samples; info has spp, passes, noise (None before two passes) and
+    converged.  kw: Film's precision, device, n_shards, shard, row_block."""
+    if batch <= 0:
+        from .errors import RtInvalid
+        raise RtInvalid("batch must be positive")
+    max_spp = int(settings.cs_samplesPerPixel if max_spp is None else max_spp)
+    with Film(world, settings, seed, **kw) as film:
+        spp, passes, figure, converged = 0, 0, None, False
+        while spp < max_spp:
+            n = min(batch, max_spp - spp)
+            film.add(n)
+            spp, passes = spp + n, passes + 1
+            if passes >= 2:
+                figure = film.noise()
+                if figure <= noise:
+                    converged = True
+                    break
+        return film.image(), dict(spp=spp, passes=passes, noise=figure, converged=converged)
