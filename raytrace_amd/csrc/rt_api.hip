@@ -305,6 +305,7 @@ int render_async(const rt_device_scene* s, const rt_camera_settings* cs, uint64_
   P.trav_exit_pct = sizeof(R) == 8 ? s->trav_exit_pct64 : s->trav_exit_pct;
   P.out_frame_rows = frame_rows;
   P.sample0 = sample0;
+  rt_host_match_target(*s->host, s->variant, P);  // (the redirect pdf deferred to the next segment, or not)
   HIP_TRY(hipSetDevice(s->device));
   // stream-ordered workspace: fixed-point sums, NaN flags, queue counter (graph-capturable)
   const size_t tile_pixels = (size_t)P.tile_rows * P.cam.width;

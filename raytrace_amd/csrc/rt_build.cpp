@@ -1112,6 +1112,11 @@ int rt_host_make_params(const rt_camera_settings* cs, uint64_t seed, const rt_ex
   P.cam.spp = cs->samples_per_pixel;
   P.cam.max_depth = cs->max_recursion_depth;
   P.cam.bg_kind = cs->background_kind;
+  // (the rounded fields, as camera_ray would compare them)
+  P.cam_defocus = 0;
+  for (int k = 0; k < 3; ++k) P.cam_defocus |= P.cam.disk_u[k] != (R)0 || P.cam.disk_v[k] != (R)0;
+  P.target_defer = 0;  // rt_host_match_target, which needs the scene, may set them
+  P.target_rec = -1;
   // redirect targets (Ray.hs:138-151)
   double cum = 0, psum = 0;
   P.n_targets = cs->n_redirect_targets;
@@ -1146,6 +1151,66 @@ int rt_host_make_params(const rt_camera_settings* cs, uint64_t seed, const rt_ex
   P.tile_rows = rows;
   return RT_OK;
 }
+
+// The redirect target as a record of the flat surface set.  A target and a parallelogram built from
+// the same q, u, v get the same n, q, wa, wb (the same binary64 expressions, rounded once to R:
+// fill_geometry, rt_host_make_params; both normals are unit, so no scale is needed), and then the
+// next segment's test of that record computes what the scatter's target test would: the same
+// plane, origin and direction.  Matched only where the old and the new order are the same
+// estimator: one target (the pdf's one term), no media (every segment starts at a scatter), a
+// diffuse flat class (the one scatter site that defers), a record tested by the quad loop (static,
+// outside the box groups) whose material ends the path, so no ray ever starts on it.
+// (rt_host_match_records: the match itself, over P's own record pointers, which must be host
+// memory — the scene's host arrays here, the host emulator's arguments in rt_trace.h.)
+template <class R>
+int rt_host_match_records(KernelParamsT<R>& P) {
+  P.target_defer = 0;
+  P.target_rec = -1;
+  if (const char* e = rt_knob("RT_AMD_TARGET_DEFER"))
+    if (atoi(e) == 0) return 0;
+  // a pinned kernel variant (experiments) compares the flat kernel with the BVH kernels on one
+  // scene bit for bit; only the flat classes can defer, so under it none does
+  if (rt_knob("RT_AMD_VARIANT")) return 0;
+  if (P.n_targets != 1 || P.n_media != 0 || !P.flat_recs || !P.prim_shade) return 0;
+  const DevFlatSet& S = P.flat_sets[0];
+  const DevTargetT<R>& T = P.targets[0];
+  for (int k = S.first; k < S.end_quad; ++k) {
+    const R* f = P.flat_recs + 16 * (size_t)k;
+    if (std::memcmp(f, T.n, 3 * sizeof(R)) || std::memcmp(f + 4, T.q, 3 * sizeof(R)) ||
+        std::memcmp(f + 8, T.wa, 3 * sizeof(R)) || std::memcmp(f + 12, T.wb, 3 * sizeof(R)))
+      continue;
+    int kf, slot;
+    std::memcpy(&kf, f + 3, 4);
+    std::memcpy(&slot, f + 11, 4);
+    if (kf != 1 || slot < 0 || slot >= P.n_prims) continue;  // (a static parallelogram)
+    if (P.prim_shade[slot].kind >= 2) continue;  // rays leave this surface: lightSource / pitchBlack only
+    P.target_defer = 1;
+    P.target_rec = k;
+    return 1;
+  }
+  return 0;
+}
+template <class R>
+int rt_host_match_target(const HostScene& H, int variant, KernelParamsT<R>& P) {
+  P.target_defer = 0;
+  P.target_rec = -1;
+  if (!H.flat || (variant & RT_VAR_BASE) != RT_VAR_FLAT || (variant & (RT_VAR_MATS | RT_VAR_MEDIA))) return 0;
+  const HostArraysT<R>& A = H.arrays<R>();
+  KernelParamsT<R> Q = P;  // the scene's records where the host can read them
+  Q.flat_recs = A.flat_recs.data();
+  Q.prim_shade = A.prim_shade.data();
+  Q.n_prims = (int)A.prim_shade.size();
+  Q.n_media = H.n_media;
+  Q.flat_sets[0] = H.flat_sets[0];
+  rt_host_match_records(Q);
+  P.target_defer = Q.target_defer;
+  P.target_rec = Q.target_rec;
+  return P.target_defer;
+}
+template int rt_host_match_records<float>(KernelParamsT<float>&);
+template int rt_host_match_records<double>(KernelParamsT<double>&);
+template int rt_host_match_target<float>(const HostScene&, int, KernelParamsT<float>&);
+template int rt_host_match_target<double>(const HostScene&, int, KernelParamsT<double>&);
 
 bool rt_host_media_late(const HostScene& H) {
   if (H.n_media == 0) return false;

@@ -351,8 +351,20 @@ struct KernelParamsT {
   FastDiv div_width, div_block;  // image width, row block
   // first sample index of this launch: the items cover samples [sample0, sample0 + cam.spp) of
   // every pixel (rt_trace.h open_item).  0 for a one-shot render; a film pass continues where the
-  // last one ended (rt_film.hip).  Last member: code that zero-fills the struct renders from 0
+  // last one ended (rt_film.hip).  Code that zero-fills the struct renders from 0
   int sample0;
+  // Deferred redirect pdf (rt_build.cpp rt_host_match_target, rt_trace.h lane_loop_lockstep): 1
+  // when the scene's one redirect target IS a static parallelogram of the flat surface set
+  // (flat_recs[target_rec], bit for bit the target's n, q, wa, wb) whose material ends the path.
+  // The scatter then leaves the target's term of the mixture pdf to the next segment's test of
+  // that record, which intersects the same ray with the same plane anyway.  0: every other scene;
+  // the scatter tests its targets itself.  Members after sample0 are appended: the earlier
+  // offsets are those of every earlier build (tests/test_target_defer.py)
+  int target_defer;
+  int target_rec;   // index into flat_recs (-1: none, never equal to a record's index)
+  // the camera has a defocus disk (cam.disk_u or cam.disk_v is not zero): camera_ray's test as one
+  // scalar integer compare instead of six binary64 VALU compares on scalar operands
+  int cam_defocus;
 };
 using DevMaterial = DevMaterialT<float>;
 using DevTexture = DevTextureT<float>;
@@ -427,6 +439,15 @@ bool rt_host_media_late(const HostScene& H);
 template <class R>
 int rt_host_make_params(const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex, KernelParamsT<R>& P,
                         std::string& err);
+// the deferred redirect pdf (KernelParams::target_defer, target_rec) of a render of H by the kernel
+// class of `variant`, from P's targets (after rt_host_make_params); returns target_defer.  Env
+// RT_AMD_TARGET_DEFER=0 (experiments) leaves it 0: the scatter's own target test
+template <class R>
+int rt_host_match_target(const HostScene& H, int variant, KernelParamsT<R>& P);
+// the same match over P's own flat_recs / prim_shade / flat_sets[0] / n_prims / n_media, which must
+// be host memory (the host emulator's arguments; a flat diffuse class is the caller's to know)
+template <class R>
+int rt_host_match_records(KernelParamsT<R>& P);
 // work decomposition (rt_build.cpp): chunk so that items >= ~8 x resident lanes
 template <class R>
 void rt_host_plan_work(KernelParamsT<R>& P, long long resident_lanes, bool two_sizes, bool lone = false);  // two_sizes: flat kernel

@@ -101,6 +101,7 @@ extern thread_local long long counters[4];
 #undef RT_HUGE
 #undef RT_R2I
 #undef RT_SINCOS_TURNS
+#undef RT_SINCOS_TURNS_S
 #undef RT_LOG
 #undef RT_RSQRT
 #undef RT_RCP
@@ -137,6 +138,7 @@ extern thread_local long long counters[4];
 // of 2 pi u by an exact quadrant reduction and polynomials — each within ~1 ulp of the correctly
 // rounded result (tools/microbench/f64_math_check.hip measures it), 2-5x fewer instructions.
 #define RT_SINCOS_TURNS(x, s, c) rt_math64::sincos_turns(x, s, c)
+#define RT_SINCOS_TURNS_S(x, s, c) rt_math64::sincos_turns<true>(x, s, c)
 #define RT_RSQRT(x) rt_math64::rsqrt(x)
 #define RT_RCP(x) rt_math64::rcp(x)
 #define RT_RCP_NZ(x) rt_math64::rcp_nz(x)
@@ -202,13 +204,23 @@ namespace rt_math64 {
 RT_MATH64_TAB const double rt_sincos_tab[2 * RT_SINCOS_TABLE_N] = RT_SINCOS_TABLE_INIT;
 // (a table-free version — quadrant reduction and fdlibm's minimax kernels, 3.25 ulp — ran Cornell
 // 4.89 -> 5.42 ms: the table's two loads cost less than the longer polynomials; profiles/r5/variants)
+// kCoefScalar (the flat lane loop, which sits at the cap of its occupancy's VGPRs): the 1 / 120
+// coefficient is set here, in a scalar register pair, every call.  Otherwise the compiler hoists it
+// out of the persistent lane loop into a VGPR pair held for the whole kernel (a binary64 literal
+// is no inline operand) — the pair the deferred redirect pdf needs across the closest hit, which
+// spilled without this.  The same arithmetic, the same bits.
+template <bool kCoefScalar = false>
 RT_MATH64_FN void sincos_turns(double u, double* sn, double* cs) {
   const double kq = __builtin_rint(u * (double)RT_SINCOS_TABLE_N);
   const double b = __builtin_fma(kq, -1.0 / RT_SINCOS_TABLE_N, u);
   const int k = (int)kq & (RT_SINCOS_TABLE_N - 1);
   const double sa = rt_sincos_tab[2 * k], ca = rt_sincos_tab[2 * k + 1];
   const double x = b * 6.283185307179586, x2 = x * x;
-  double ps = __builtin_fma(x2, -1.0 / 5040.0, 1.0 / 120.0);
+  double c120 = 1.0 / 120.0;
+#ifndef RT_HOST_EMU
+  if constexpr (kCoefScalar) asm volatile("" : "+s"(c120));
+#endif
+  double ps = __builtin_fma(x2, -1.0 / 5040.0, c120);
   ps = __builtin_fma(x2, ps, -1.0 / 6.0);
   const double sb = __builtin_fma(x2 * x, ps, x);
   double pc = __builtin_fma(x2, -1.0 / 720.0, 1.0 / 24.0);
@@ -377,11 +389,19 @@ RT_FN real u01(uint32_t w) { return (real)(w >> 8) * (RL(1.0) / RL(16777216.0));
 // the binary64 Cornell kernel and ran 0.5-2 % slower: profiles/r6/flat)
 
 // uniform direction on the unit sphere (the distribution of randomUnitVector, Core.hs:54-60)
+// kFlatLoop: called from the flat lane loop (binary64: rt_math64::sincos_turns kCoefScalar)
+#ifndef RT_SINCOS_TURNS_S
+#define RT_SINCOS_TURNS_S RT_SINCOS_TURNS
+#endif
+template <bool kFlatLoop = false>
 RT_FN f3 unit_vector(uint32_t a, uint32_t b) {
   real z = RL(1.0) - RL(2.0) * u01(a);
   real r = RT_SQRT(RMAX(RL(0.0), RL(1.0) - z * z));
   real s, c;
-  RT_SINCOS_TURNS(u01(b), &s, &c);
+  if constexpr (kFlatLoop)
+    RT_SINCOS_TURNS_S(u01(b), &s, &c);
+  else
+    RT_SINCOS_TURNS(u01(b), &s, &c);
   return mk3(r * c, r * s, z);
 }
 
@@ -580,15 +600,25 @@ RT_FN void isect_sphere(const PrimRec& r, f3 o, const RayCtx& R, real tmin, real
 }
 // planeShape (Geometry.hs:117-144): parallelogram a, b in [0,1]; triangle a, b >= 0, a + b <= 1.
 // kQuad: 1 parallelogram, 0 triangle, -1 either (per-lane `quad`, a select instead of a branch)
+// tgt_term (kQuad == 1 only; the record is the scene's redirect target, KernelParams::target_rec):
+// what target_hit and the mixture pdf make of the same numbers, t^2 / |n . d| where the ray meets
+// the parallelogram on (0, infinity) — target_hit's own conditions, without tmin and self — else 0
 template <int kQuad>
 RT_FN void isect_plane(const PrimRec& r, f3 o, const RayCtx& R, real tmin_up, bool self, real& t, real& q,
-                       bool quad = false) {
+                       bool quad = false, real* tgt_term = nullptr) {
   f3 n = xyz(r.a);
   real denom = dot(n, R.d);
   f3 qo = xyz(r.b) - o;
   t = dot(n, qo) * RT_RCP_NZ(denom);  // |denom| <= 1e-8 (NaN t included) fails the margin m2
   f3 prel = t * R.d - qo;
   real aa = dot(prel, xyz(r.c)), bb = dot(prel, xyz(r.e));
+  if constexpr (kQuad == 1) {
+    if (tgt_term) {
+      const real in = RMIN(RMIN(aa, bb), RMIN(RL(1.0) - aa, RL(1.0) - bb));
+      const bool hit = (RABS(denom) > RL(1e-8)) & (t > RL(0.0)) & (in >= RL(0.0));
+      *tgt_term = hit ? t * t * RABS(RT_RCP_NZ(denom)) : RL(0.0);  // (the reciprocal t was made with)
+    }
+  }
   real m1, m2 = RMIN(RABS(denom) - RL(1e-8), t - tmin_up);
   if constexpr (kQuad < 0) {  // quad: min(1 - a, 1 - b); triangle: 1 - a - b
     m1 = RMIN(RMIN(aa, bb), quad ? RMIN(RL(1.0) - aa, RL(1.0) - bb) : RL(1.0) - aa - bb);
@@ -650,14 +680,15 @@ RT_FN void test_rec(const KernelParams& P, const PrimRec& r, int pi, const RayCt
 
 // A static primitive of a known kind (flat sets are grouped by class: rt_build.cpp).
 template <int kKind, bool kKeyOnly = true, bool kInst = false>
-RT_FN void test_static(const PrimRec& r, const RayCtx& R, real tmin, real tmin_up, Closest& C, int pi = 0) {
+RT_FN void test_static(const PrimRec& r, const RayCtx& R, real tmin, real tmin_up, Closest& C, int pi = 0,
+                       real* tgt_term = nullptr) {
   RT_COUNT(1);
   const bool self = is_self<kInst>(R, RT_R2I(r.b.w), -1);  // a world leaf
   real t, q;
   if constexpr (kKind == RT_PRIM_CLASS_SPHERE)
     isect_sphere(r, R.o, R, tmin, tmin_up, self, t, q);
   else
-    isect_plane<kKind == RT_PRIM_CLASS_QUAD ? 1 : 0>(r, R.o, R, tmin_up, self, t, q);
+    isect_plane<kKind == RT_PRIM_CLASS_QUAD ? 1 : 0>(r, R.o, R, tmin_up, self, t, q, false, tgt_term);
   consider<kKeyOnly, kInst>(C, t, q, RT_R2I(r.c.w), pi, -1);
 }
 
@@ -1286,13 +1317,13 @@ RT_FN void test_leaf_generic(const KernelParams& P, RC& R, TravState& S) {
 
 // kFlat: the set is one flat leaf (rt_internal.h DevFlatSet); every lane walks the same
 // records in the same order, so the loops are coherent and the records are scalar loads.
-template <>
-RT_FN_SPEC void closest<true>(const KernelParams& P, cfp prims, int root, int set, const RayCtx& R, real tmin, Closest& C,
-                         const Trav& W, int* overflow) {
-  (void)prims;
-  (void)root;
-  (void)W;
-  (void)overflow;
+// kDefer (the diffuse flat classes; KernelParams::target_defer): the test of the record that is the
+// redirect target (target_rec; -1 in every other scene, no record's index) also adds the target's
+// term of the mixture pdf of the scatter this ray left, prob_icr t^2 / |n . d|, to `apdf`, which
+// that scatter set to the pdf's other term (mixture_scatter) — one uniform compare per
+// parallelogram, the same records and loads
+template <bool kDefer>
+RT_FN void closest_flat(const KernelParams& P, int set, const RayCtx& R, real tmin, Closest& C, real* apdf = nullptr) {
   {
     // set comes from the kernel arguments: the ranges are wave-uniform, every loop is scalar
     const DevFlatSet& S = P.flat_sets[set];
@@ -1300,7 +1331,17 @@ RT_FN_SPEC void closest<true>(const KernelParams& P, cfp prims, int root, int se
     for (int b = S.box_first; b < S.box_end; ++b) test_box<true>((const RT_CAS DevBox*)P.boxes + b, R, tmin_up, C);
     int k = S.first;
     const RT_CAS PrimRec64* rp = (const RT_CAS PrimRec64*)P.flat_recs + k;  // one 64-B scalar load per record
-    for (; k < S.end_quad; ++k, ++rp) test_static<RT_PRIM_CLASS_QUAD>(ld_rec64(rp), R, tmin, tmin_up, C);
+    for (; k < S.end_quad; ++k, ++rp) {
+      if constexpr (kDefer) {
+        if (k == P.target_rec) {
+          real term;
+          test_static<RT_PRIM_CLASS_QUAD>(ld_rec64(rp), R, tmin, tmin_up, C, 0, &term);
+          *apdf = RFMA(P.targets[0].prob_icr, term, *apdf);
+          continue;
+        }
+      }
+      test_static<RT_PRIM_CLASS_QUAD>(ld_rec64(rp), R, tmin, tmin_up, C);
+    }
     for (; k < S.end_tri; ++k, ++rp) test_static<RT_PRIM_CLASS_TRI>(ld_rec64(rp), R, tmin, tmin_up, C);
     for (; k < S.end_sphere; ++k, ++rp) test_static<RT_PRIM_CLASS_SPHERE>(ld_rec64(rp), R, tmin, tmin_up, C);
     for (; k < S.end; ++k, ++rp) test_rec<true>(P, ld_rec64(rp), k, R, tmin, tmin_up, C);
@@ -1314,6 +1355,15 @@ RT_FN_SPEC void closest<true>(const KernelParams& P, cfp prims, int root, int se
     }
 #endif
   }
+}
+template <>
+RT_FN_SPEC void closest<true>(const KernelParams& P, cfp prims, int root, int set, const RayCtx& R, real tmin, Closest& C,
+                         const Trav& W, int* overflow) {
+  (void)prims;
+  (void)root;
+  (void)W;
+  (void)overflow;
+  closest_flat<false>(P, set, R, tmin, C);
 }
 
 // BVH set (lockstep variant): resumable rounds run to completion.
@@ -1431,9 +1481,15 @@ RT_FN void medium_event(const KernelParams& P, int m, uint32_t pix, int sample, 
 // when a HemisphereF direction is below the surface (pdf1 <= 0: the path ends, Ray.hs:198).
 // kEarly: return there, newdir and Tf untouched (the full-material kernels, whose register
 // allocation needs the short exit); otherwise they are written either way.
-template <bool kMats, bool kEarly>
+// kDefer (the diffuse flat lane loop) with KernelParams::target_defer set: the one target is a
+// record of the surface set, which the next segment tests against this very ray (closest_flat), so
+// the target loop is left to it: Tf = f pdf1, *apdf = remProb pdf1, and the lane loop divides the
+// throughput by the whole pdf once that test has added the target's term.  Same draws, same
+// branches; the throughput factor's roundings come in another order.
+template <bool kMats, bool kEarly, class... Defer>
 RT_FN bool mixture_scatter(const KernelParams& P, const HitInfo& h, const RayCtx& R, const u4& w, const DevMaterial& Mt,
-                           bool hemi, f3 tex, f3& newdir, f3& Tf) {
+                           bool hemi, f3 tex, f3& newdir, f3& Tf, Defer... apdf) {
+  constexpr bool kDefer = sizeof...(Defer) == 1;  // (the diffuse flat lane loop passes its real*)
   real cr = u01(w.x);
   int choice = -1;
   for (int k = 0; k < P.n_targets; ++k) {
@@ -1443,7 +1499,19 @@ RT_FN bool mixture_scatter(const KernelParams& P, const HitInfo& h, const RayCtx
     }
   }
   f3 dir;
-  if (choice < 0) {
+  // one normalisation after the join of the two samplers (the same arithmetic per lane, so the
+  // same bits; a wave with lanes on both sides issues it once; Cornell binary64 -2.5 %,
+  // profiles/target_defer): the diffuse flat classes, whose scatter is always hemispherical
+  if constexpr (kDefer) {
+    if (choice < 0) {
+      dir = h.n + unit_vector<true>(w.y, w.z);
+    } else {
+      const DevTarget& Tg = P.targets[choice];
+      f3 lp = ld3(Tg.q) + u01(w.y) * ld3(Tg.u) + u01(w.z) * ld3(Tg.v);
+      dir = lp - h.p;
+    }
+    dir = normalize(dir);
+  } else if (choice < 0) {
     f3 uu = unit_vector(w.y, w.z);
     dir = hemi ? normalize(h.n + uu) : uu;
   } else {
@@ -1454,6 +1522,14 @@ RT_FN bool mixture_scatter(const KernelParams& P, const HitInfo& h, const RayCtx
   real pdf1 = hemi ? dot(dir, h.n) * (RL(1.0) / kPi) : RL(0.25) / kPi;
   if constexpr (kEarly)
     if (hemi && pdf1 <= RL(0.0)) return false;
+  if constexpr (kDefer && !kMats && !kEarly) {
+    if (P.target_defer) {  // wave-uniform (a kernel argument)
+      *(apdf, ...) = P.rem_prob * pdf1;
+      Tf = pdf1 * tex;
+      newdir = dir;
+      return !(hemi && pdf1 <= RL(0.0));
+    }
+  }
   real mix = RL(0.0);
   for (int k = 0; k < P.n_targets; ++k) {
     // p t^2 / |(u x v) . dir| (Ray.hs:202) with (u x v) . dir = |u x v| (n . dir): the target
@@ -1483,10 +1559,10 @@ RT_FN bool mixture_scatter(const KernelParams& P, const HitInfo& h, const RayCtx
 // (and seg).  Returns true when the path terminates.
 // kMats: the scene has materials beyond lightSource / pitchBlack / lambertian; their code is
 // compiled only into those instantiations (the Cornell box and the bunny have none: -2.4 % / -1.2 %)
-template <int kTex, bool kMats, bool kInst>
+template <int kTex, bool kMats, bool kInst, class... Defer>
 RT_FN bool shade_event(const KernelParams& P, cfp prims, uint32_t pix, int sample, int seg, real tbest, int best,
                        int hit_medium, const RayCtx& R, f3& L, const f3& T, int best_inst, f3& np, f3& nd, f3& Tf,
-                       int& ngid) {
+                       int& ngid, Defer... apdf) {
   RT_HOOK_SEGMENT(pix, sample, seg, R, tbest, best, hit_medium, L, T);
   if (hit_medium < 0 && best < 0) {
     // miss: cs_background (Ray.hs:179)
@@ -1563,7 +1639,7 @@ RT_FN bool shade_event(const KernelParams& P, cfp prims, uint32_t pix, int sampl
     // diffuse, so their lanes cost nothing extra, and the direction and weight come out defined
     // on every path without a terminating branch of their own
     if (Mt.kind == 0) L = L + T * tex;  // lightSource: emit
-    terminate = !mixture_scatter<false, false>(P, h, R, w, Mt, true, tex, newdir, Tf) || Mt.kind < 2;
+    terminate = !mixture_scatter<false, false>(P, h, R, w, Mt, true, tex, newdir, Tf, apdf...) || Mt.kind < 2;
   } else {
     switch (Mt.kind) {
       case 0:  // lightSource: emit, Absorb
@@ -1628,9 +1704,9 @@ RT_FN bool shade_event(const KernelParams& P, cfp prims, uint32_t pix, int sampl
 // before camera_ray (the emulator tests fail otherwise).  Keeping the unchanged ray on the
 // terminating exits instead cost the flat binary64 kernel ~40 copies per lane-loop iteration
 // (round 4).
-template <int kTex, bool kMats, bool kInst = false>
+template <int kTex, bool kMats, bool kInst = false, class... Defer>
 RT_FN bool shade(const KernelParams& P, cfp prims, uint32_t pix, int sample, int& seg, real tbest, int best,
-                 int hit_medium, RayCtx& R, f3& L, f3& T, int best_inst = -1) {
+                 int hit_medium, RayCtx& R, f3& L, f3& T, int best_inst = -1, Defer... apdf) {
 #ifdef RT_HOST_EMU
   // poison on the CPU: a path that ends leaves R, T and the self ids undefined (NaN / an id no leaf
   // has) until camera_ray restarts it, so an emulator test fails if anything reads them in between
@@ -1650,7 +1726,8 @@ RT_FN bool shade(const KernelParams& P, cfp prims, uint32_t pix, int sample, int
   int ngid = R.self_gid;
 #endif
   const bool term =
-      shade_event<kTex, kMats, kInst>(P, prims, pix, sample, seg, tbest, best, hit_medium, R, L, T, best_inst, np, nd, Tf, ngid);
+      shade_event<kTex, kMats, kInst>(P, prims, pix, sample, seg, tbest, best, hit_medium, R, L, T, best_inst, np, nd, Tf,
+                                      ngid, apdf...);
   R.o = np;
   R.d = nd;
   T = T * Tf;
@@ -1744,6 +1821,32 @@ RT_FN bool steal_sample(bool thief, ItemCtx& I, int tp_plain) {
 }
 #endif
 
+// camera_ray of the flat lane loop, which runs it in every iteration (some lane starts a path): the
+// pixel from pxgy, and the defocus disk by the host's flag (KernelParams::cam_defocus: some disk_u /
+// disk_v field is not zero).  The scalar unit has no floating-point compare, so the six field tests
+// above are six VALU compares on scalar operands per iteration (Cornell binary64 -0.9 %,
+// profiles/target_defer).  A function of its own: camera_ray's source in any other shape (a flag
+// variable, a template, a shared tail) reorders a few hundred instructions of every BVH kernel,
+// and left as it is those kernels come out as before, to the instruction.
+RT_FN void camera_ray_flat(const KernelParams& P, uint32_t pix, int sample, uint32_t pxgy, RayCtx& R) {
+  const int gy = (int)(pxgy >> 16), px = (int)(pxgy & 0xffffu);
+  u4 w0 = philox(pix, (uint32_t)sample, 0u, RT_EV_CAMERA0, P.key0, P.key1);
+  R.time_w = w0.z;
+  f3 origin = ld3(P.cam.center);
+  if (P.cam_defocus) {
+    u4 w1 = philox(pix, (uint32_t)sample, 0u, RT_EV_CAMERA1, P.key0, P.key1);
+    real rad = RT_SQRT(u01(w0.w)), s, c;
+    RT_SINCOS_TURNS_S(u01(w1.x), &s, &c);
+    origin = origin + (rad * c) * ld3(P.cam.disk_u) + (rad * s) * ld3(P.cam.disk_v);
+  }
+  f3 target = ld3(P.cam.top_left) + ((real)px + u01(w0.x)) * ld3(P.cam.pixel_u) +
+              ((real)gy + u01(w0.y)) * ld3(P.cam.pixel_v);
+  R.o = origin;
+  R.d = normalize(target - origin);
+  R.self_gid = -1;
+  R.self_inst = -1;
+}
+
 // The lockstep persistent lane loop.  `work.grab(need, slot)` is wave-collective: it
 // returns a fresh item for lanes with need == true (and its aggregation slot); `work.commit(c,
 // tile_pixel, acc, bad)`, also wave-collective, adds the finished items' sums of lanes with
@@ -1751,7 +1854,17 @@ RT_FN bool steal_sample(bool thief, ItemCtx& I, int tp_plain) {
 // kernel (every lane tests the same primitives), and the lockstep BVH variant kept for
 // experiments (RT_VAR_BVH_LOCKSTEP; BVH scenes, media or not, default to lane_loop_bvh).
 template <bool kFlat, int kTex, bool kMedia, bool kMats, class Work, class AccT>
-RT_FN int lane_loop_lockstep(const KernelParams& P0, Work& work, const Trav& TW, const real* prims_, AccT& acc) {
+RT_FN int lane_loop_lockstep(const KernelParams& P0_, Work& work, const Trav& TW, const real* prims_, AccT& acc) {
+#ifdef RT_HOST_EMU
+  // the host emulator has no launch path of its own: the deferred redirect pdf of its arguments is
+  // matched here, by the host's own function, over the records it holds in host memory
+  KernelParams Pm = P0_;
+  if constexpr (kFlat && !kMedia && !kMats) rt_host_match_records(Pm);
+  const KernelParams& P0 = Pm;
+#else
+  const KernelParams& P0 = P0_;
+#endif
+  (void)P0;
   const cfp prims = cf(prims_);
   int overflow = 0;
   ItemCtx I{-1, 0, 0, 0u, 0u};
@@ -1762,6 +1875,12 @@ RT_FN int lane_loop_lockstep(const KernelParams& P0, Work& work, const Trav& TW,
   // T: the path throughput.  No radiance register across iterations (as lane_loop_bvh): only the
   // event that ends a path emits, so a sample's radiance is that one term, summed at once.
   f3 T = mk3(RL(1.), RL(1.), RL(1.));
+  // the deferred redirect pdf (KernelParams::target_defer; the diffuse flat classes): the mixture
+  // pdf of the scatter the current ray left, short of the target's term until this segment's
+  // closest hit has tested the target's record.  Undefined on a path's first segment (as T and
+  // the ray of a path that ended: NaN in the host emulator)
+  constexpr bool kDefer = kFlat && !kMedia && !kMats;
+  real apdf = RL(1.);
   RayCtx R;
   R.o = R.d = mk3(RL(0.), RL(0.), RL(0.));
 #if RT_NODE_F32
@@ -1803,7 +1922,10 @@ RT_FN int lane_loop_lockstep(const KernelParams& P0, Work& work, const Trav& TW,
     RT_PROF_MARK(PF_FRONT);
     RT_PROF_ADD(PF_CAM_LANES, RT_BALLOT_COUNT(!alive));
     if (!alive) {
-      camera_ray(P, I.pix, I.sample, I.pxgy, R);
+      if constexpr (kFlat)
+        camera_ray_flat(P, I.pix, I.sample, I.pxgy, R);
+      else
+        camera_ray(P, I.pix, I.sample, I.pxgy, R);
       T = mk3(RL(1.), RL(1.), RL(1.));
       seg = 0;
       alive = true;
@@ -1813,7 +1935,14 @@ RT_FN int lane_loop_lockstep(const KernelParams& P0, Work& work, const Trav& TW,
     // ---- closest hit over the surfaces and every medium (Ray.hs:178)
     if constexpr (!kFlat) prep_ray(R);  // reciprocal direction: BVH slab tests only
     Closest C = no_hit();
-    closest<kFlat>(P, prims, P.surface_root, 0, R, kTmin, C, TW, &overflow);
+    if constexpr (kDefer) {
+      closest_flat<true>(P, 0, R, kTmin, C, &apdf);
+      // the throughput over the whole mixture pdf, before anything reads it (the background, the
+      // emission, the next scatter); a path's first segment left no scatter (a select: 1)
+      if (P.target_defer) T = (seg == 0 ? RL(1.) : RT_RCP(apdf)) * T;  // wave-uniform branch
+    } else {
+      closest<kFlat>(P, prims, P.surface_root, 0, R, kTmin, C, TW, &overflow);
+    }
     real tbest = C.t;
     const int best = C.prim;
     int hit_medium = -1;
@@ -1847,8 +1976,16 @@ RT_FN int lane_loop_lockstep(const KernelParams& P0, Work& work, const Trav& TW,
     }
     RT_PROF_MARK(PF_TRAV);
     f3 L = mk3(RL(0.), RL(0.), RL(0.));
-    if (shade<kTex, kMats>(P, prims, I.pix, I.sample, seg, tbest, best, hit_medium, R, L, T)) {
-      // the path ended: R and T are indeterminate until camera_ray (shade's invariant)
+    bool ended;
+    if constexpr (kDefer)
+      ended = shade<kTex, kMats, false>(P, prims, I.pix, I.sample, seg, tbest, best, hit_medium, R, L, T, -1, &apdf);
+    else
+      ended = shade<kTex, kMats>(P, prims, I.pix, I.sample, seg, tbest, best, hit_medium, R, L, T);
+    if (ended) {
+      // the path ended: R, T and apdf are indeterminate until camera_ray (shade's invariant)
+#ifdef RT_HOST_EMU
+      apdf = RT_NAN;
+#endif
       RT_HOOK_SAMPLE(I.pix, I.sample, L);
       acc_sample(acc, L, bad);
       alive = false;
