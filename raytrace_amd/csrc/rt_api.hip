@@ -55,38 +55,32 @@ int upload(T** dst, const std::vector<T>& src) {
 // the device copies of one precision's records (rt_internal.h HostArraysT)
 template <class R>
 struct DevArrays {
-  R* prims = nullptr;
-  DevMaterialT<R>* prim_shade = nullptr;
-  R* prim_uv = nullptr;
-  DevMaterialT<R>* mats = nullptr;
-  DevTextureT<R>* texs = nullptr;
-  R* motions = nullptr;
-  R* uvframes = nullptr;
-  R* texels = nullptr;
-  R* perlin_grad = nullptr;
-  R* flat_recs = nullptr;
-  DevBoxT<R>* boxes = nullptr;
-  DevInstanceT<R>* instances = nullptr;
-  DevMediumT<R> media[RT_MAX_MEDIA];
+  SceneRecordsT<R> rec;     // device pointers; nodes and perlin_perm are the scene's (both precisions share them)
+  void* owned[12] = {};     // the allocations behind rec, to free
+  int n_owned = 0;
   int resident_blocks = 0;  // render-kernel workgroups resident on the device (occupancy query)
   int lds_nodes = 0;        // top surface-BVH nodes this precision's kernel stages in LDS per workgroup
-  int upload(const HostArraysT<R>& H) {
+  template <class T>
+  int put(const T*& dst, const std::vector<T>& src) {
+    T* d = nullptr;
+    const int rc = ::upload(&d, src);
+    dst = d;
+    owned[n_owned++] = d;
+    return rc;
+  }
+  int upload(const HostArraysT<R>& H, const float* nodes, const int* perlin_perm) {
+    rec.nodes = nodes, rec.perlin_perm = perlin_perm;
     int rc;
-    if ((rc = ::upload(&prims, H.prims)) || (rc = ::upload(&prim_shade, H.prim_shade)) ||
-        (rc = ::upload(&prim_uv, H.prim_uv)) || (rc = ::upload(&mats, H.mats)) || (rc = ::upload(&texs, H.texs)) ||
-        (rc = ::upload(&motions, H.motions)) || (rc = ::upload(&uvframes, H.uvframes)) ||
-        (rc = ::upload(&flat_recs, H.flat_recs)) || (rc = ::upload(&boxes, H.boxes)) ||
-        (rc = ::upload(&texels, H.texels)) || (rc = ::upload(&perlin_grad, H.perlin_grad)) ||
-        (rc = ::upload(&instances, H.instances)))
+    if ((rc = put(rec.prims, H.prims)) || (rc = put(rec.prim_shade, H.prim_shade)) ||
+        (rc = put(rec.prim_uv, H.prim_uv)) || (rc = put(rec.mats, H.mats)) || (rc = put(rec.texs, H.texs)) ||
+        (rc = put(rec.motions, H.motions)) || (rc = put(rec.uvframes, H.uvframes)) ||
+        (rc = put(rec.flat_recs, H.flat_recs)) || (rc = put(rec.boxes, H.boxes)) || (rc = put(rec.texels, H.texels)) ||
+        (rc = put(rec.perlin_grad, H.perlin_grad)) || (rc = put(rec.instances, H.instances)))
       return rc;
-    for (int k = 0; k < RT_MAX_MEDIA; ++k) media[k] = H.media[k];
     return RT_OK;
   }
   void release() {
-    for (void* p : {(void*)prims, (void*)prim_shade, (void*)prim_uv, (void*)mats, (void*)texs, (void*)motions,
-                    (void*)uvframes, (void*)texels, (void*)perlin_grad, (void*)flat_recs, (void*)boxes,
-                    (void*)instances})
-      (void)hipFree(p);
+    for (int k = 0; k < n_owned; ++k) (void)hipFree(owned[k]);
   }
 };
 
@@ -104,12 +98,6 @@ struct rt_device_scene {
   mutable DevArrays<float> f32;
   mutable DevArrays<double> f64;
   mutable bool have_f32 = false, have_f64 = false;
-  int leaf_exit_pct = 100, leaf_exit_pct64 = 100;
-  int trav_exit_pct = 50, trav_exit_pct64 = 50;
-  int surface_root = RT_EMPTY_ROOT;
-  int n_media = 0;
-  DevFlatSet flat_sets[1 + RT_MAX_MEDIA];
-  int n_nodes = 0, n_prims = 0, max_depth = 0;
   int stack_depth = 1;       // LDS stack entries per lane
   int variant = RT_VAR_FLAT;  // render-kernel variant (rt_internal.h RT_VAR_*)
   double build_ms = 0;       // host scene build (shared by every device of a multi-device scene)
@@ -207,7 +195,7 @@ int ensure_precision(const rt_device_scene* s) {
   auto t0 = std::chrono::steady_clock::now();
   HIP_TRY(hipSetDevice(s->device));
   DevArrays<R>& A = s->arrays<R>();
-  int rc = A.upload(s->host->arrays<R>());
+  int rc = A.upload(s->host->arrays<R>(), s->nodes, s->perlin_perm);
   if (rc) {
     A.release();
     A = DevArrays<R>();
@@ -268,44 +256,20 @@ int render_async(const rt_device_scene* s, const rt_camera_settings* cs, uint64_
   if (int rc = ensure_precision<R>(s)) return rc;
   lone = lone || (ex && (ex->flags & RT_EXEC_SOLO));  // (the caller says this render runs alone)
   const DevArrays<R>& A = s->arrays<R>();
+  constexpr bool f64 = sizeof(R) == 8;
+  LaunchInputs L;
+  L.resident_lanes = (long long)A.resident_blocks * rt_class_block(f64, rt_class_of(f64, s->variant));
+  L.lds_nodes = A.lds_nodes;
+  L.lone = lone;
+  L.sample0 = sample0;
+  L.out_frame_rows = frame_rows;
+  if (const char* e = rt_knob("RT_AMD_POOL_SHIFT")) L.pool_shift = std::max(4, std::min(10, atoi(e)));
   KernelParamsT<R> P;
-  std::memset(&P, 0, sizeof P);
-  if (lone && (s->variant & RT_VAR_BASE) == RT_VAR_FLAT) P.pool_shift = 6;
-  if (const char* e = rt_knob("RT_AMD_POOL_SHIFT")) P.pool_shift = std::max(4, std::min(10, atoi(e)));
   std::string err;
-  int rc = rt_host_make_params(cs, seed, ex, P, err);
+  int rc = rt_host_render_params(*s->host, s->variant, A.rec, cs, seed, ex, L, P, err);
   if (rc) return fail(rc, "%s", err.c_str());
-  P.nodes = s->nodes;
-  P.prims = A.prims;
-  P.prim_shade = A.prim_shade;
-  P.prim_uv = A.prim_uv;
-  P.mats = A.mats;
-  P.texs = A.texs;
-  P.motions = A.motions;
-  P.uvframes = A.uvframes;
-  P.texels = A.texels;
-  P.perlin_perm = s->perlin_perm;
-  P.perlin_grad = A.perlin_grad;
-  P.flat_recs = A.flat_recs;
-  P.boxes = A.boxes;
-  P.instances = A.instances;
   P.status = s->status;
   P.out = d_out;
-  P.surface_root = s->surface_root;
-  P.leaf_exit_pct = sizeof(R) == 8 ? s->leaf_exit_pct64 : s->leaf_exit_pct;
-  P.surface_prefix = (s->variant & RT_VAR_BASE) != RT_VAR_FLAT && s->n_nodes > 0 ? 1 : 0;
-  P.n_media = s->n_media;
-  for (int k = 0; k < s->n_media; ++k) P.media[k] = A.media[k];
-  for (int k = 0; k <= RT_MAX_MEDIA; ++k) P.flat_sets[k] = s->flat_sets[k];
-  P.stack_depth = s->stack_depth;
-  P.lds_nodes = A.lds_nodes;
-  P.n_prims = s->n_prims;
-  const KernelClass c = rt_class_of(sizeof(R) == 8, s->variant);
-  rt_host_plan_work(P, (long long)A.resident_blocks * rt_class_block(sizeof(R) == 8, c), c.var == RT_VAR_FLAT, lone);
-  P.trav_exit_pct = sizeof(R) == 8 ? s->trav_exit_pct64 : s->trav_exit_pct;
-  P.out_frame_rows = frame_rows;
-  P.sample0 = sample0;
-  rt_host_match_target(*s->host, s->variant, P);  // (the redirect pdf deferred to the next segment, or not)
   HIP_TRY(hipSetDevice(s->device));
   // stream-ordered workspace: fixed-point sums, NaN flags, queue counter (graph-capturable)
   const size_t tile_pixels = (size_t)P.tile_rows * P.cam.width;
@@ -387,19 +351,8 @@ int upload_common(const std::shared_ptr<const HostScene>& Hp, int device, rt_dev
     destroy_scene(s);
     return rc;
   }
-  s->surface_root = H.surface_root;
-  s->leaf_exit_pct = H.leaf_exit_pct;
-  s->leaf_exit_pct64 = H.leaf_exit_pct64;
-  s->trav_exit_pct = H.trav_exit_pct;
-  s->trav_exit_pct64 = H.trav_exit_pct64;
-  s->n_media = H.n_media;
-  for (int k = 0; k <= RT_MAX_MEDIA; ++k) s->flat_sets[k] = H.flat_sets[k];
-  s->n_nodes = H.n_nodes;
-  s->n_prims = H.n_prims;
-  s->max_depth = H.max_depth;
-  s->stack_depth = H.max_depth > 1 ? H.max_depth : 1;
-  s->variant = rt_host_variant(H.flat, H.n_media, H.noise, H.full_mats, H.uv_tex, H.n_instances > 0, H.leaf_kind,
-                               rt_host_media_late(H), s->stack_depth);
+  s->stack_depth = rt_host_stack_depth(H);
+  s->variant = rt_host_variant(H);
   s->upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   *out = s;
   return RT_OK;
@@ -586,8 +539,8 @@ int render_one(rt_multi_scene* M, const rt_camera_settings* cs, uint64_t seed, c
     stats->upload_ms = build_ms + M->upload_ms + prep_ms;
     stats->kernel_ms = ms;
     stats->samples = (int64_t)rows * cs->image_width * cs->samples_per_pixel;
-    stats->bvh_nodes = s->n_nodes;
-    stats->max_stack = s->max_depth;
+    stats->bvh_nodes = s->host->n_nodes;
+    stats->max_stack = s->host->max_depth;
     stats->device_allocs = allocs;
     stats->kernel_block = rt_class_block(!f32, rt_class_of(!f32, s->variant));
     stats->total_ms = build_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -748,8 +701,8 @@ int multi_render(rt_multi_scene* M, const rt_camera_settings* cs, uint64_t seed,
     stats->upload_ms = build_ms + M->upload_ms + prep;
     stats->kernel_ms = ms;
     stats->samples = (int64_t)rows_out * cs->image_width * cs->samples_per_pixel;
-    stats->bvh_nodes = M->scenes[0]->n_nodes;
-    stats->max_stack = M->scenes[0]->max_depth;
+    stats->bvh_nodes = M->scenes[0]->host->n_nodes;
+    stats->max_stack = M->scenes[0]->host->max_depth;
     stats->device_allocs = allocs;
     stats->kernel_block = rt_class_block(!f32, rt_class_of(!f32, M->scenes[0]->variant));
     stats->total_ms = build_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -875,7 +828,7 @@ int rt_scene_stats(const rt_device_scene* s, rt_stats* st) {
   if (!s || !st) return fail(RT_E_INVALID, "null argument");
   std::memset(st, 0, sizeof *st);
   st->upload_ms = s->build_ms + s->upload_ms;
-  st->bvh_nodes = s->n_nodes;
+  st->bvh_nodes = s->host->n_nodes;
   st->max_stack = s->stack_depth;
   return RT_OK;
 }

@@ -1060,6 +1060,10 @@ int rt_host_variant(bool flat, int n_media, bool noise, bool mats, bool tex, boo
   return v | (noise ? RT_VAR_NOISE : 0) | (n_media > 0 ? RT_VAR_MEDIA : 0) | (mats ? RT_VAR_MATS : 0) |
          (tex ? RT_VAR_TEX : 0) | leaf | (v == RT_VAR_BVH ? late : 0) | narrow;
 }
+int rt_host_variant(const HostScene& H) {
+  return rt_host_variant(H.flat, H.n_media, H.noise, H.full_mats, H.uv_tex, H.n_instances > 0, H.leaf_kind,
+                         rt_host_media_late(H), rt_host_stack_depth(H));
+}
 
 template <class R>
 int rt_host_make_params(const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex, KernelParamsT<R>& P,
@@ -1159,58 +1163,91 @@ int rt_host_make_params(const rt_camera_settings* cs, uint64_t seed, const rt_ex
 // plane, origin and direction.  Matched only where the old and the new order are the same
 // estimator: one target (the pdf's one term), no media (every segment starts at a scatter), a
 // diffuse flat class (the one scatter site that defers), a record tested by the quad loop (static,
-// outside the box groups) whose material ends the path, so no ray ever starts on it.
-// (rt_host_match_records: the match itself, over P's own record pointers, which must be host
-// memory — the scene's host arrays here, the host emulator's arguments in rt_trace.h.)
+// outside the box groups) whose material ends the path, so no ray ever starts on it.  The match
+// reads the scene's host arrays.
 template <class R>
-int rt_host_match_records(KernelParamsT<R>& P) {
+int rt_host_match_target(const HostScene& H, int variant, KernelParamsT<R>& P) {
   P.target_defer = 0;
   P.target_rec = -1;
+  if (!H.flat || (variant & RT_VAR_BASE) != RT_VAR_FLAT || (variant & (RT_VAR_MATS | RT_VAR_MEDIA))) return 0;
   if (const char* e = rt_knob("RT_AMD_TARGET_DEFER"))
     if (atoi(e) == 0) return 0;
   // a pinned kernel variant (experiments) compares the flat kernel with the BVH kernels on one
   // scene bit for bit; only the flat classes can defer, so under it none does
   if (rt_knob("RT_AMD_VARIANT")) return 0;
-  if (P.n_targets != 1 || P.n_media != 0 || !P.flat_recs || !P.prim_shade) return 0;
-  const DevFlatSet& S = P.flat_sets[0];
+  const HostArraysT<R>& A = H.arrays<R>();  // (the host's copy: P's record pointers may be a device's)
+  if (P.n_targets != 1 || H.n_media != 0 || A.flat_recs.empty() || A.prim_shade.empty()) return 0;
+  const DevFlatSet& S = H.flat_sets[0];
   const DevTargetT<R>& T = P.targets[0];
   for (int k = S.first; k < S.end_quad; ++k) {
-    const R* f = P.flat_recs + 16 * (size_t)k;
+    const R* f = A.flat_recs.data() + 16 * (size_t)k;
     if (std::memcmp(f, T.n, 3 * sizeof(R)) || std::memcmp(f + 4, T.q, 3 * sizeof(R)) ||
         std::memcmp(f + 8, T.wa, 3 * sizeof(R)) || std::memcmp(f + 12, T.wb, 3 * sizeof(R)))
       continue;
     int kf, slot;
     std::memcpy(&kf, f + 3, 4);
     std::memcpy(&slot, f + 11, 4);
-    if (kf != 1 || slot < 0 || slot >= P.n_prims) continue;  // (a static parallelogram)
-    if (P.prim_shade[slot].kind >= 2) continue;  // rays leave this surface: lightSource / pitchBlack only
+    if (kf != 1 || slot < 0 || slot >= (int)A.prim_shade.size()) continue;  // (a static parallelogram)
+    if (A.prim_shade[slot].kind >= 2) continue;  // rays leave this surface: lightSource / pitchBlack only
     P.target_defer = 1;
     P.target_rec = k;
     return 1;
   }
   return 0;
 }
+
 template <class R>
-int rt_host_match_target(const HostScene& H, int variant, KernelParamsT<R>& P) {
-  P.target_defer = 0;
-  P.target_rec = -1;
-  if (!H.flat || (variant & RT_VAR_BASE) != RT_VAR_FLAT || (variant & (RT_VAR_MATS | RT_VAR_MEDIA))) return 0;
+SceneRecordsT<R> rt_host_records(const HostScene& H) {
   const HostArraysT<R>& A = H.arrays<R>();
-  KernelParamsT<R> Q = P;  // the scene's records where the host can read them
-  Q.flat_recs = A.flat_recs.data();
-  Q.prim_shade = A.prim_shade.data();
-  Q.n_prims = (int)A.prim_shade.size();
-  Q.n_media = H.n_media;
-  Q.flat_sets[0] = H.flat_sets[0];
-  rt_host_match_records(Q);
-  P.target_defer = Q.target_defer;
-  P.target_rec = Q.target_rec;
-  return P.target_defer;
+  SceneRecordsT<R> r;
+  r.nodes = H.nodes.data(), r.perlin_perm = H.perlin_perm.data();
+  r.prims = A.prims.data(), r.prim_uv = A.prim_uv.data(), r.motions = A.motions.data();
+  r.uvframes = A.uvframes.data(), r.texels = A.texels.data(), r.perlin_grad = A.perlin_grad.data();
+  r.flat_recs = A.flat_recs.data(), r.prim_shade = A.prim_shade.data(), r.mats = A.mats.data();
+  r.texs = A.texs.data(), r.boxes = A.boxes.data(), r.instances = A.instances.data();
+  return r;
 }
-template int rt_host_match_records<float>(KernelParamsT<float>&);
-template int rt_host_match_records<double>(KernelParamsT<double>&);
-template int rt_host_match_target<float>(const HostScene&, int, KernelParamsT<float>&);
-template int rt_host_match_target<double>(const HostScene&, int, KernelParamsT<double>&);
+
+template <class R>
+int rt_host_render_params(const HostScene& H, int variant, const SceneRecordsT<R>& r, const rt_camera_settings* cs,
+                          uint64_t seed, const rt_exec* ex, const LaunchInputs& L, KernelParamsT<R>& P,
+                          std::string& err) {
+  constexpr bool f64 = sizeof(R) == 8;
+  const bool flat = (variant & RT_VAR_BASE) == RT_VAR_FLAT;
+  std::memset(&P, 0, sizeof P);
+  if (int rc = rt_host_make_params(cs, seed, ex, P, err)) return rc;
+  P.nodes = r.nodes, P.perlin_perm = r.perlin_perm;
+  P.prims = r.prims, P.prim_uv = r.prim_uv, P.motions = r.motions, P.uvframes = r.uvframes, P.texels = r.texels;
+  P.perlin_grad = r.perlin_grad, P.flat_recs = r.flat_recs, P.prim_shade = r.prim_shade, P.mats = r.mats;
+  P.texs = r.texs, P.boxes = r.boxes, P.instances = r.instances;
+  P.surface_root = H.surface_root;
+  P.leaf_exit_pct = f64 ? H.leaf_exit_pct64 : H.leaf_exit_pct;
+  // flat_sets[0] is a prefix only beside a BVH.  A scene without nodes that is not flat (an instance
+  // alone, over RT_LDS_PRIMS_MAX leaves in single-leaf sets) has none: its flat_sets[0] is empty
+  P.surface_prefix = !flat && H.n_nodes > 0 ? 1 : 0;
+  P.n_media = H.n_media;
+  for (int k = 0; k < H.n_media; ++k) P.media[k] = H.arrays<R>().media[k];
+  for (int k = 0; k <= RT_MAX_MEDIA; ++k) P.flat_sets[k] = H.flat_sets[k];
+  P.stack_depth = rt_host_stack_depth(H);
+  P.lds_nodes = L.lds_nodes;
+  P.n_prims = H.n_prims;
+  // (a synchronous call's flat kernel: 64-id pools, rt_api.hip render_async)
+  P.pool_shift = L.pool_shift ? L.pool_shift : L.lone && flat ? 6 : 0;
+  rt_host_plan_work(P, L.resident_lanes, flat, L.lone);
+  P.trav_exit_pct = f64 ? H.trav_exit_pct64 : H.trav_exit_pct;
+  P.out_frame_rows = L.out_frame_rows;
+  P.sample0 = L.sample0;
+  rt_host_match_target(H, variant, P);
+  return RT_OK;
+}
+#define RT_INSTANTIATE(R)                                                                                           \
+  template int rt_host_match_target<R>(const HostScene&, int, KernelParamsT<R>&);                                   \
+  template SceneRecordsT<R> rt_host_records<R>(const HostScene&);                                                   \
+  template int rt_host_render_params<R>(const HostScene&, int, const SceneRecordsT<R>&, const rt_camera_settings*, \
+                                        uint64_t, const rt_exec*, const LaunchInputs&, KernelParamsT<R>&, std::string&);
+RT_INSTANTIATE(float)
+RT_INSTANTIATE(double)
+#undef RT_INSTANTIATE
 
 bool rt_host_media_late(const HostScene& H) {
   if (H.n_media == 0) return false;

@@ -143,10 +143,6 @@
 // rt_knob returns null and every caller (a Haskell program with a stray variable in its
 // environment included) gets the measured defaults.
 const char* rt_knob(const char* name);
-// host choice of variant (rt_build.cpp); knob RT_AMD_VARIANT overrides the base for experiments.
-// media_late: every medium's boundary is the surface set or a single leaf (rt_host_media_late)
-int rt_host_variant(bool flat, int n_media, bool noise, bool mats, bool tex, bool inst = false, int leaf_kind = 0,
-                    bool media_late = false, int stack_depth = 1);
 
 #define RT_KIND_MASK 3
 #define RT_FLAG_MOTION 4
@@ -324,8 +320,8 @@ struct KernelParamsT {
   // class); 0: every item adds to `accum` directly
   int agg_big, agg_small;
   // ids per work-queue pool, 1 << pool_shift (rt_render_kernel.h WaveWork): RT_POOL for renders
-  // whose frames overlap (rt_render_async), 64 for the flat kernels' synchronous calls (rt_api.hip
-  // render_async `lone`), whose one launch ends on the pools still held when the queue drains
+  // whose frames overlap (rt_render_async), 64 for the flat kernels' synchronous calls (LaunchInputs::
+  // lone, rt_host_render_params), whose one launch ends on the pools still held when the queue drains
   int pool_shift;
   int stack_depth;            // LDS stack entries per lane (>= the scene's BVH depth)
   int lds_nodes;              // BVH nodes [0, lds_nodes) are read from the workgroup's LDS copy
@@ -353,7 +349,8 @@ struct KernelParamsT {
   // every pixel (rt_trace.h open_item).  0 for a one-shot render; a film pass continues where the
   // last one ended (rt_film.hip).  Code that zero-fills the struct renders from 0
   int sample0;
-  // Deferred redirect pdf (rt_build.cpp rt_host_match_target, rt_trace.h lane_loop_lockstep): 1
+  // Deferred redirect pdf (rt_build.cpp rt_host_match_target, in rt_host_render_params; read by
+  // rt_trace.h lane_loop_lockstep): 1
   // when the scene's one redirect target IS a static parallelogram of the flat surface set
   // (flat_recs[target_rec], bit for bit the target's n, q, wa, wb) whose material ends the path.
   // The scatter then leaves the target's term of the mixture pdf to the next segment's test of
@@ -435,19 +432,54 @@ int rt_host_shard_rows(int height, const rt_exec* ex);
 // the same for every lane: the BVH kernels can run the media events in the shading phase
 // (RT_VAR_MEDIA_LATE; rt_trace.h media_events_late)
 bool rt_host_media_late(const HostScene& H);
+// the render-kernel variant of a scene (RT_VAR_*); knob RT_AMD_VARIANT overrides the base for experiments
+int rt_host_variant(const HostScene& H);
+// ... from the scene's properties one by one (media_late: rt_host_media_late; stack_depth: below)
+int rt_host_variant(bool flat, int n_media, bool noise, bool mats, bool tex, bool inst, int leaf_kind, bool media_late,
+                    int stack_depth);
+// LDS stack entries per lane of a scene's kernels (KernelParams::stack_depth): its BVH depth, at least 1
+inline int rt_host_stack_depth(const HostScene& H) { return H.max_depth > 1 ? H.max_depth : 1; }
 // fills camera / targets / tiling / key of P (pointers are left to the caller); R = float, double
 template <class R>
 int rt_host_make_params(const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex, KernelParamsT<R>& P,
                         std::string& err);
-// the deferred redirect pdf (KernelParams::target_defer, target_rec) of a render of H by the kernel
-// class of `variant`, from P's targets (after rt_host_make_params); returns target_defer.  Env
-// RT_AMD_TARGET_DEFER=0 (experiments) leaves it 0: the scatter's own target test
+// The record pointers of one precision, in host memory (rt_host_records) or in a device's (rt_api.hip
+// DevArrays): the fill below copies them and never reads through them
+template <class R>
+struct SceneRecordsT {
+  const float* nodes = nullptr;
+  const int* perlin_perm = nullptr;
+  const R *prims = nullptr, *prim_uv = nullptr, *motions = nullptr, *uvframes = nullptr, *texels = nullptr;
+  const R *perlin_grad = nullptr, *flat_recs = nullptr;
+  const DevMaterialT<R>*prim_shade = nullptr, *mats = nullptr;
+  const DevTextureT<R>* texs = nullptr;
+  const DevBoxT<R>* boxes = nullptr;
+  const DevInstanceT<R>* instances = nullptr;
+};
+template <class R>
+SceneRecordsT<R> rt_host_records(const HostScene& H);  // H's own arrays
+// what only the caller of a render knows
+struct LaunchInputs {
+  long long resident_lanes = 0;  // lanes the render grid keeps resident (rt_host_plan_work)
+  int lds_nodes = 0;             // KernelParams::lds_nodes
+  bool lone = false;             // a synchronous call's one launch (rt_api.hip render_async)
+  int sample0 = 0, out_frame_rows = 0;
+  int pool_shift = 0;            // 4-10: KernelParams::pool_shift whatever the plan would choose
+};
+// The whole argument block of one render of H by the kernel class of `variant`, but for the
+// workspace and output pointers (out, status, accum, nanflag, counter: left null): P zeroed, then
+// rt_host_make_params, the record pointers, the scene's scalars, media and flat sets, the stack
+// depth, rt_host_plan_work and the deferred redirect pdf (KernelParams::target_defer, target_rec;
+// env RT_AMD_TARGET_DEFER=0, experiments, leaves it 0: the scatter's own target test).  Host records
+// are read through H only, so `records` may point anywhere.  The library's renders (rt_api.hip) and
+// the host emulator (tests/kernel_emu) both get their arguments here.
+template <class R>
+int rt_host_render_params(const HostScene& H, int variant, const SceneRecordsT<R>& records,
+                          const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex, const LaunchInputs& L,
+                          KernelParamsT<R>& P, std::string& err);
+// the deferred redirect pdf alone (part of rt_host_render_params), from P's targets and H's records; returns target_defer
 template <class R>
 int rt_host_match_target(const HostScene& H, int variant, KernelParamsT<R>& P);
-// the same match over P's own flat_recs / prim_shade / flat_sets[0] / n_prims / n_media, which must
-// be host memory (the host emulator's arguments; a flat diffuse class is the caller's to know)
-template <class R>
-int rt_host_match_records(KernelParamsT<R>& P);
 // work decomposition (rt_build.cpp): chunk so that items >= ~8 x resident lanes
 template <class R>
 void rt_host_plan_work(KernelParamsT<R>& P, long long resident_lanes, bool two_sizes, bool lone = false);  // two_sizes: flat kernel

@@ -1854,17 +1854,7 @@ RT_FN void camera_ray_flat(const KernelParams& P, uint32_t pix, int sample, uint
 // kernel (every lane tests the same primitives), and the lockstep BVH variant kept for
 // experiments (RT_VAR_BVH_LOCKSTEP; BVH scenes, media or not, default to lane_loop_bvh).
 template <bool kFlat, int kTex, bool kMedia, bool kMats, class Work, class AccT>
-RT_FN int lane_loop_lockstep(const KernelParams& P0_, Work& work, const Trav& TW, const real* prims_, AccT& acc) {
-#ifdef RT_HOST_EMU
-  // the host emulator has no launch path of its own: the deferred redirect pdf of its arguments is
-  // matched here, by the host's own function, over the records it holds in host memory
-  KernelParams Pm = P0_;
-  if constexpr (kFlat && !kMedia && !kMats) rt_host_match_records(Pm);
-  const KernelParams& P0 = Pm;
-#else
-  const KernelParams& P0 = P0_;
-#endif
-  (void)P0;
+RT_FN int lane_loop_lockstep(const KernelParams& P0, Work& work, const Trav& TW, const real* prims_, AccT& acc) {
   const cfp prims = cf(prims_);
   int overflow = 0;
   ItemCtx I{-1, 0, 0, 0u, 0u};

@@ -51,6 +51,27 @@ def render(settings, world, seed, n_shards=1, shard=0, row_block=4, nthreads=Non
     return out
 
 
+def render_params(settings, world, seed, n_shards=1, shard=0, row_block=4, chunk=0, precision="f64"):
+    """{member: [values]} of the KernelParams render() builds for these arguments (rt_emu_render_params:
+    every number exactly, as a double; a pointer as 0.0 for null or 1.0)."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from raytrace_amd import _lib as R
+    from raytrace_amd.ray import _seed64
+    from raytrace_amd.scene import FlatScene, flatten
+    flat = world if isinstance(world, FlatScene) else flatten(world)
+    cs, sc, ex = R.camera_struct(settings), R.scene_struct(flat), R.exec_struct(0, n_shards, shard, row_block)
+    names, counts, values, n = (ctypes.c_char_p * 128)(), (ctypes.c_int * 128)(), np.zeros(1024), (ctypes.c_int * 2)()
+    rc = lib().rt_emu_render_params(ctypes.byref(cs), ctypes.byref(sc), ctypes.c_uint64(_seed64(seed)), ctypes.byref(ex),
+                                    ctypes.c_int(precision == "f64"), ctypes.c_int(chunk), names, counts, 128,
+                                    values.ctypes.data_as(ctypes.c_void_p), len(values), n)
+    if rc != 0:
+        raise RuntimeError(f"rt_emu_render_params failed {rc}: {lib().rt_emu_last_error().decode()}")
+    assert n[0] <= 128 and n[1] <= len(values), (n[0], n[1])
+    ends = np.cumsum(counts[:n[0]])
+    return {names[i].decode(): values[ends[i] - counts[i]:ends[i]].tolist() for i in range(n[0])}
+
+
 def scene_info(world):
     """n_nodes, surface_nodes, max_depth, n_prims, flat, box groups, surface-prefix primitives and
     the one-class leaf kind (1 static triangles, 2 static spheres, 0 mixed) of the host build of

@@ -67,41 +67,15 @@ void* worker(void* arg) {
   return nullptr;
 }
 
-// one render of the host scene in this precision; out: tile_rows x width x 3 reals
-int render(const HostScene& H, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex, RT_NS::real* out,
-           int nthreads, int chunk, long long* counters, std::string& err) {
-  using real = RT_NS::real;
-  const HostArraysT<real>& A = H.arrays<real>();
-  RT_NS::KernelParams P = {};
-  int rc = rt_host_make_params(cs, seed, ex, P, err);
-  if (rc) return rc;
-  P.nodes = H.nodes.data();
-  P.prims = A.prims.data();
-  P.prim_shade = A.prim_shade.data();
-  P.prim_uv = A.prim_uv.data();
-  P.mats = A.mats.data();
-  P.texs = A.texs.data();
-  P.motions = A.motions.data();
-  P.uvframes = A.uvframes.data();
-  P.texels = A.texels.data();
-  P.perlin_perm = H.perlin_perm.data();
-  P.perlin_grad = A.perlin_grad.data();
-  P.flat_recs = A.flat_recs.data();
-  P.boxes = A.boxes.data();
-  P.instances = A.instances.data();
+// the kernel arguments of one render of the host scene in this precision: the library's own fill
+// (rt_build.cpp rt_host_render_params) over the host's records, as an overlapped render on 4096
+// resident lanes with no nodes in LDS; `chunk` > 0 overrides the plan with one item size
+int params(const HostScene& H, int variant, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex,
+           RT_NS::real* out, int chunk, RT_NS::KernelParams& P, std::string& err) {
+  LaunchInputs L;
+  L.resident_lanes = 4096;
+  if (int rc = rt_host_render_params(H, variant, rt_host_records<RT_NS::real>(H), cs, seed, ex, L, P, err)) return rc;
   P.out = out;
-  P.surface_root = H.surface_root;
-  P.leaf_exit_pct = RT_F64 ? H.leaf_exit_pct64 : H.leaf_exit_pct;
-  P.surface_prefix = H.flat ? 0 : 1;
-  P.n_media = H.n_media;
-  for (int k = 0; k < H.n_media; ++k) P.media[k] = A.media[k];
-  for (int k = 0; k <= RT_MAX_MEDIA; ++k) P.flat_sets[k] = H.flat_sets[k];
-  P.stack_depth = H.max_depth > 1 ? H.max_depth : 1;
-  P.n_prims = H.n_prims;
-  const int variant = rt_host_variant(H.flat, H.n_media, H.noise, H.full_mats, H.uv_tex, H.n_instances > 0, H.leaf_kind,
-                                      rt_host_media_late(H), H.max_depth > 1 ? H.max_depth : 1);
-  rt_host_plan_work(P, 4096, (variant & RT_VAR_BASE) == RT_VAR_FLAT);
-  P.trav_exit_pct = RT_F64 ? H.trav_exit_pct64 : H.trav_exit_pct;
   if (chunk > 0) {
     P.chunk = chunk;
     P.n_chunks = (P.cam.spp + chunk - 1) / chunk;
@@ -111,6 +85,16 @@ int render(const HostScene& H, const rt_camera_settings* cs, uint64_t seed, cons
     P.div_small = rt_host_fastdiv((uint32_t)P.n_chunks);
     P.n_items = P.n_chunks * P.tile_rows * P.cam.width;
   }
+  return RT_OK;
+}
+
+// one render of the host scene in this precision; out: tile_rows x width x 3 reals
+int render(const HostScene& H, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex, RT_NS::real* out,
+           int nthreads, int chunk, long long* counters, std::string& err) {
+  using real = RT_NS::real;
+  RT_NS::KernelParams P;
+  const int variant = rt_host_variant(H);
+  if (int rc = params(H, variant, cs, seed, ex, out, chunk, P, err)) return rc;
   const size_t tile_pixels = (size_t)P.tile_rows * P.cam.width;
   const size_t w = RT_ACC_WORDS(real);
   std::vector<std::atomic<long long>> accum(tile_pixels * w);

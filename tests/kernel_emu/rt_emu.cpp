@@ -13,6 +13,7 @@
 #include "../../include/rt.h"
 #include "../../raytrace_amd/csrc/rt_internal.h"
 #include "../../raytrace_amd/csrc/rt_kernel_class.h"
+#include "../target_defer/kp_members.h"
 // The device's FP32 reciprocal (v_rcp_f32) is within 1 ulp of 1/x, not correctly rounded:
 // rt_emu_set_rcp_ulps(k) makes the emulator's reciprocal the IEEE result moved k ulps (k < 0:
 // toward -inf), so the node test's conservativeness check covers both roundings the device can
@@ -128,6 +129,90 @@ int rt_emu_scene_info(const rt_scene* sc, int* info) {
   }
   info[6] = pre;
   info[7] = H.leaf_kind;
+  return RT_OK;
+}
+}
+
+// The kernel arguments of a render (test tooling, tests/test_render_params.py): every member of
+// KernelParams (../target_defer/kp_members.h) by name with its values as doubles (exact for every
+// int, uint32, float and double), records field by field (no padding), pointers as null (0) or not (1).
+namespace {
+struct ParamsDump {
+  const char** names;
+  int* counts;
+  double* values;
+  int cap_members, cap_values, m = 0, v = 0;
+  template <class T>
+  void add(const T& x) {  // T: an arithmetic type or a pointer
+    if (v < cap_values) {
+      if constexpr (std::is_pointer_v<T>) values[v] = x != nullptr;
+      else values[v] = (double)x;
+    }
+    ++v;
+  }
+  template <class T, size_t N>
+  void add(const T (&a)[N]) {
+    for (const T& x : a) add(x);
+  }
+  void add(const FastDiv& d) { add(d.m), add(d.s), add(d.d), add(d.pad); }
+  void add(const DevFlatSet& d) {
+    add(d.first), add(d.end_quad), add(d.end_tri), add(d.end_sphere), add(d.end), add(d.box_first), add(d.box_end),
+        add(d.pad);
+  }
+  template <class R>
+  void add(const DevMediumT<R>& d) {
+    add(d.neg_inv_density), add(d.material), add(d.root), add(d.alias_surface);
+  }
+  template <class R>
+  void add(const DevTargetT<R>& d) {
+    add(d.q), add(d.u), add(d.v), add(d.n), add(d.wa), add(d.wb), add(d.cr), add(d.prob), add(d.thresh), add(d.prob_icr);
+  }
+  template <class R>
+  void add(const DevCameraT<R>& d) {
+    add(d.center), add(d.top_left), add(d.pixel_u), add(d.pixel_v), add(d.disk_u), add(d.disk_v), add(d.bg0), add(d.bg1);
+    add(d.width), add(d.height), add(d.spp), add(d.max_depth), add(d.bg_kind), add(d.pad);
+  }
+  template <class T>
+  void member(const char* name, const T& x) {
+    const int v0 = v;
+    add(x);
+    if (m < cap_members) names[m] = name, counts[m] = v - v0;
+    ++m;
+  }
+  template <class R>
+  void all(const KernelParamsT<R>& P) {
+#define RT_EMU_KP_ONE(x) member(#x, P.x);
+    RT_TD_KP_MEMBERS(RT_EMU_KP_ONE)
+#undef RT_EMU_KP_ONE
+  }
+};
+}  // namespace
+
+extern "C" {
+// the arguments emu32 / emu64 render() gives the lane loop for this scene, settings and rt_exec;
+// names / counts: one entry per member (at most cap_members are written), values: the members'
+// values back to back (at most cap_values); n_out[0] = members, n_out[1] = values
+int rt_emu_render_params(const rt_camera_settings* cs, const rt_scene* sc, uint64_t seed, const rt_exec* ex, int f64,
+                         int chunk, const char** names, int* counts, int cap_members, double* values, int cap_values,
+                         int* n_out) {
+  HostScene H;
+  int rc = rt_host_build_scene(sc, H, g_err);
+  if (rc) return rc;
+  ParamsDump D{names, counts, values, cap_members, cap_values};
+  const int variant = rt_host_variant(H);
+  if (f64) {
+    double out = 0;
+    rtk64::KernelParams P;
+    if ((rc = emu64::params(H, variant, cs, seed, ex, &out, chunk, P, g_err))) return rc;
+    D.all(P);
+  } else {
+    float out = 0;
+    rtk::KernelParams P;
+    if ((rc = emu32::params(H, variant, cs, seed, ex, &out, chunk, P, g_err))) return rc;
+    D.all(P);
+  }
+  n_out[0] = D.m;
+  n_out[1] = D.v;
   return RT_OK;
 }
 }

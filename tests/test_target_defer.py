@@ -1,4 +1,4 @@
-"""The deferred redirect pdf of the diffuse flat kernels (rt_build.cpp rt_host_match_target,
+"""The deferred redirect pdf of the diffuse flat kernels (rt_build.cpp rt_host_render_params,
 rt_trace.h lane_loop_lockstep / closest_flat / mixture_scatter; KernelParams::target_defer).
 
 When the scene's one redirect target is, bit for bit, a static parallelogram of the flat surface
