@@ -4,6 +4,8 @@
 // concurrent uploads, shard renders on per-device streams, a device-side gather by peer copies
 // into the first device's framebuffer and ONE device-to-host copy), the 8-bit output epilogue,
 // the progressive film (its state and entry points; kernels in rt_film.hip), error reporting.
+// A synchronous render (render_sync) runs render_one (one device) or render_many (a thread per
+// shard) over the same stages: prepare_part, enqueue_shard, enqueue_readback, fill_stats.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,6 +45,24 @@ int fail(int code, const char* fmt, ...) {
     hipError_t e_ = (expr);                                                                 \
     if (e_ != hipSuccess) return fail(RT_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
+
+using Clock = std::chrono::steady_clock;
+double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+
+bool exec_f32(const rt_exec* ex) { return ex && (ex->flags & RT_EXEC_F32) != 0; }
+int acc_words_of(bool f32) { return f32 ? RT_ACC_WORDS(float) : RT_ACC_WORDS(double); }
+size_t elem_size_of(bool f32) { return f32 ? sizeof(float) : sizeof(double); }
+int prec_bit(bool f32) { return f32 ? 1 : 2; }  // ensure_precisions' mask
+
+// the workspace of one render: fixed-point sums at 0, NaN flags at off_flag, queue head words at
+// off_ctr (every part 256-byte aligned, zeroed slack behind the sums and the flags: rt_film.hip
+// reads both as 16-byte vectors)
+struct Workspace { size_t off_flag, off_ctr, bytes; };
+Workspace workspace_layout(size_t tile_pixels, int acc_words) {
+  const size_t of = (tile_pixels * acc_words * sizeof(long long) + 255) & ~(size_t)255;
+  const size_t oc = of + ((tile_pixels * sizeof(unsigned) + 255) & ~(size_t)255);
+  return {of, oc, oc + 256 * 8};  // up to 8 queue head words (rt_render_kernel.h RT_QUEUES)
+}
 
 template <class T>
 int upload(T** dst, const std::vector<T>& src) {
@@ -173,8 +193,8 @@ struct rt_film {
   unsigned long long* total = nullptr;
   unsigned int* flags = nullptr;
   double* q = nullptr;
-  char* ws = nullptr;
-  size_t ws_bytes = 0;
+  char* ws = nullptr;  // a pass's workspace, laid out as ws_lay
+  Workspace ws_lay{};
   void* tile = nullptr;
   double* partial_sum = nullptr;
   int* partial_cnt = nullptr;
@@ -185,14 +205,13 @@ struct rt_film {
 
 namespace {
 
-// one render of the scene's records of precision R, enqueued on `stream`
 // the records of precision R on the scene's device (uploaded on first use) and their kernel's
 // resident workgroups; thread-safe
 template <class R>
 int ensure_precision(const rt_device_scene* s) {
   std::lock_guard<std::mutex> lock(s->mu);
   if (s->have<R>()) return RT_OK;
-  auto t0 = std::chrono::steady_clock::now();
+  auto t0 = Clock::now();
   HIP_TRY(hipSetDevice(s->device));
   DevArrays<R>& A = s->arrays<R>();
   int rc = A.upload(s->host->arrays<R>(), s->nodes, s->perlin_perm);
@@ -224,22 +243,11 @@ int ensure_precision(const rt_device_scene* s) {
     return fail(RT_E_HIP, "occupancy query failed");
   }
   s->have<R>() = true;
-  s->upload_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  s->upload_ms += ms_since(t0);
   return RT_OK;
 }
 
-// the stream-ordered workspace of one render: fixed-point sums, NaN flags, queue head words
-size_t workspace_bytes(size_t tile_pixels, int acc_words, size_t* off_flag, size_t* off_ctr) {
-  // (every part 256-byte aligned, zeroed slack behind the sums and the flags: rt_film.hip reads
-  // both as 16-byte vectors)
-  const size_t of = (tile_pixels * acc_words * sizeof(long long) + 255) & ~(size_t)255;
-  const size_t oc = of + ((tile_pixels * sizeof(unsigned) + 255) & ~(size_t)255);
-  if (off_flag) *off_flag = of;
-  if (off_ctr) *off_ctr = oc;
-  return oc + 256 * 8;  // up to 8 queue head words (rt_render_kernel.h RT_QUEUES)
-}
-
-
+// RenderCall: what a render is given besides the frame.
 // ws / ws_cap: a caller-held workspace (a multi-device scene's resident one), or null: the render
 // takes one from the stream-ordered pool (hipMallocAsync / hipFreeAsync).  lone: a synchronous
 // call's launch (rt_render, rt_multi_render), whose time includes the end of its queue: the flat
@@ -249,40 +257,46 @@ size_t workspace_bytes(size_t tile_pixels, int acc_words, size_t* off_flag, size
 // profiles/r5/pool).  Env RT_AMD_POOL_SHIFT overrides (experiments).
 // sample0 / resolve: a film pass (rt_film_add) renders samples [sample0, sample0 + spp) and leaves
 // the sums in the workspace (no mean: d_out is unused) for rt_film_merge_kernel.
+struct RenderCall {
+  void* d_out = nullptr;  // linear RGB of the render's precision, on the scene's device
+  char* ws = nullptr;
+  size_t ws_cap = 0;
+  int frame_rows = 0;     // > 0: d_out is a whole frame of that many rows (KernelParams::out_frame_rows)
+  bool lone = false, resolve = true;
+  int sample0 = 0;
+};
+
+// one render of the scene's records of precision R, enqueued on `hip_stream`
 template <class R>
-int render_async(const rt_device_scene* s, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex, R* d_out,
-                 void* hip_stream, char* ws_given = nullptr, size_t ws_cap = 0, int frame_rows = 0, bool lone = false,
-                 int sample0 = 0, bool resolve = true) {
+int render_async(const rt_device_scene* s, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex,
+                 const RenderCall& c, void* hip_stream) {
   if (int rc = ensure_precision<R>(s)) return rc;
-  lone = lone || (ex && (ex->flags & RT_EXEC_SOLO));  // (the caller says this render runs alone)
   const DevArrays<R>& A = s->arrays<R>();
   constexpr bool f64 = sizeof(R) == 8;
   LaunchInputs L;
   L.resident_lanes = (long long)A.resident_blocks * rt_class_block(f64, rt_class_of(f64, s->variant));
   L.lds_nodes = A.lds_nodes;
-  L.lone = lone;
-  L.sample0 = sample0;
-  L.out_frame_rows = frame_rows;
+  L.lone = c.lone || (ex && (ex->flags & RT_EXEC_SOLO));  // (the caller says this render runs alone)
+  L.sample0 = c.sample0;
+  L.out_frame_rows = c.frame_rows;
   if (const char* e = rt_knob("RT_AMD_POOL_SHIFT")) L.pool_shift = std::max(4, std::min(10, atoi(e)));
   KernelParamsT<R> P;
   std::string err;
   int rc = rt_host_render_params(*s->host, s->variant, A.rec, cs, seed, ex, L, P, err);
   if (rc) return fail(rc, "%s", err.c_str());
   P.status = s->status;
-  P.out = d_out;
+  P.out = (R*)c.d_out;
   HIP_TRY(hipSetDevice(s->device));
   // stream-ordered workspace: fixed-point sums, NaN flags, queue counter (graph-capturable)
-  const size_t tile_pixels = (size_t)P.tile_rows * P.cam.width;
-  size_t off_flag = 0, off_ctr = 0;
-  const size_t bytes = workspace_bytes(tile_pixels, RT_ACC_WORDS(R), &off_flag, &off_ctr);
+  const Workspace W = workspace_layout((size_t)P.tile_rows * P.cam.width, RT_ACC_WORDS(R));
   hipStream_t st = (hipStream_t)hip_stream;
-  char* ws = ws_given && ws_cap >= bytes ? ws_given : nullptr;
+  char* ws = c.ws && c.ws_cap >= W.bytes ? c.ws : nullptr;
   const bool own = ws == nullptr;
-  if (own) HIP_TRY(hipMallocAsync((void**)&ws, bytes, st));
-  HIP_TRY(hipMemsetAsync(ws, 0, bytes, st));
+  if (own) HIP_TRY(hipMallocAsync((void**)&ws, W.bytes, st));
+  HIP_TRY(hipMemsetAsync(ws, 0, W.bytes, st));
   P.accum = (unsigned long long*)ws;
-  P.nanflag = (unsigned int*)(ws + off_flag);
-  P.counter = (int*)(ws + off_ctr);
+  P.nanflag = (unsigned int*)(ws + W.off_flag);
+  P.counter = (int*)(ws + W.off_ctr);
   rc = RT_OK;
   // The persistent grid can leave RT_GRID_RESERVE workgroup slots free, so that with frames
   // overlapped on two streams this frame's resolve starts as soon as its render ends.  Measured
@@ -291,13 +305,17 @@ int render_async(const rt_device_scene* s, const rt_camera_settings* cs, uint64_
   int reserve = A.resident_blocks > 16 * RT_GRID_RESERVE ? RT_GRID_RESERVE : 0;
   if (const char* e = rt_knob("RT_AMD_GRID_RESERVE")) reserve = std::max(0, std::min(A.resident_blocks - 1, atoi(e)));
   if (rt_launch_render(P, A.resident_blocks - reserve, s->variant, hip_stream) ||
-      (resolve && rt_launch_resolve(P, hip_stream)))
+      (c.resolve && rt_launch_resolve(P, hip_stream)))
     rc = fail(RT_E_HIP, "kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
   if (own) HIP_TRY(hipFreeAsync(ws, st));
   return rc;
 }
 
-bool exec_f32(const rt_exec* ex) { return ex && (ex->flags & RT_EXEC_F32) != 0; }
+// the one precision dispatch of a render
+int render_any(const rt_device_scene* s, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex, bool f32,
+               const RenderCall& c, void* hip_stream) {
+  return f32 ? render_async<float>(s, cs, seed, ex, c, hip_stream) : render_async<double>(s, cs, seed, ex, c, hip_stream);
+}
 
 // rt_exec.flags: known bits only, at most one 8-bit encoding
 int check_flags(const rt_exec* ex) {
@@ -305,6 +323,19 @@ int check_flags(const rt_exec* ex) {
   if (ex->flags & ~known) return fail(RT_E_INVALID, "unknown rt_exec.flags bits 0x%x", ex->flags & ~known);
   if ((ex->flags & RT_EXEC_ENCODE8_SRGB) && (ex->flags & RT_EXEC_ENCODE8_SQRT))
     return fail(RT_E_INVALID, "rt_exec.flags: RT_EXEC_ENCODE8_SRGB and RT_EXEC_ENCODE8_SQRT are exclusive");
+  return RT_OK;
+}
+
+// A frame's arguments (non-null) checked before a scene is built or a device touched: image, shard,
+// flags, camera (a throw-away KernelParams).  For rt_render, rt_multi_render and rt_film_create alone.
+int validate_frame(const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex) {
+  const int h = rt_host_image_height(cs);
+  if (h <= 0 || cs->image_width <= 0) return fail(RT_E_INVALID, "image %dx%d must be non-empty", cs->image_width, h);
+  if (rt_host_shard_rows(h, ex) < 0) return fail(RT_E_INVALID, "invalid rt_exec");
+  if (int rc = check_flags(ex)) return rc;
+  KernelParams P;
+  std::string err;
+  if (int rc = rt_host_make_params(cs, seed, ex, P, err)) return fail(rc, "%s", err.c_str());
   return RT_OK;
 }
 
@@ -337,7 +368,7 @@ void destroy_scene(rt_device_scene* s) {
 // the precision-independent part of a device scene: BVH nodes, Perlin permutations, status word,
 // the kernel variant and the LDS plan; precisions follow on first render (ensure_precision)
 int upload_common(const std::shared_ptr<const HostScene>& Hp, int device, rt_device_scene** out) {
-  auto t0 = std::chrono::steady_clock::now();
+  auto t0 = Clock::now();
   const HostScene& H = *Hp;
   *out = nullptr;
   HIP_TRY(hipSetDevice(device));
@@ -353,7 +384,7 @@ int upload_common(const std::shared_ptr<const HostScene>& Hp, int device, rt_dev
   }
   s->stack_depth = rt_host_stack_depth(H);
   s->variant = rt_host_variant(H);
-  s->upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  s->upload_ms = ms_since(t0);
   *out = s;
   return RT_OK;
 }
@@ -394,7 +425,7 @@ int multi_create(const std::shared_ptr<const HostScene>& H, const int32_t* devic
   M->scenes.assign(distinct.size(), nullptr);
   std::vector<int> rcs(distinct.size(), RT_OK);
   std::vector<std::string> errs(distinct.size());
-  auto t0 = std::chrono::steady_clock::now();
+  auto t0 = Clock::now();
   {
     std::vector<std::thread> th;
     for (size_t j = 0; j < distinct.size(); ++j)
@@ -406,7 +437,7 @@ int multi_create(const std::shared_ptr<const HostScene>& H, const int32_t* devic
       });
     for (auto& t : th) t.join();
   }
-  M->upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  M->upload_ms = ms_since(t0);
   for (size_t j = 0; j < distinct.size(); ++j)
     if (rcs[j]) {
       for (rt_device_scene* s : M->scenes) destroy_scene(s);
@@ -481,48 +512,113 @@ int grow(void** p, size_t* cap, size_t need, int* allocs) {
   return RT_OK;
 }
 
+// ---- a synchronous render of a resident scene: the stages, then the two drivers that run them
+// what a render cost, for rt_stats (over shards: the longest times, every allocation)
+struct RenderCost {
+  double prep_ms = 0;   // the precision's upload, when this render is its first
+  float kernel_ms = 0;  // between the part's events e0 and e1
+  int allocs = 0;       // grow's
+};
+// where a shard's resolve writes: its own tile; its rows of the frame on the first device; or its
+// tile, which one strided copy then puts into that frame
+enum class ShardOut { tile, frame, tile_to_frame };
+
+// shard k's rt_exec: on devices[k], shard k of n for a device list, linear (encoded after the gather)
+rt_exec shard_exec(const rt_multi_scene* M, const rt_exec* ex, int k) {
+  rt_exec e = *ex;
+  e.n_devices = 0, e.devices = nullptr, e.device = M->devices[k];
+  e.flags &= ~(RT_EXEC_ENCODE8_SRGB | RT_EXEC_ENCODE8_SQRT);
+  if (M->devices.size() > 1) e.n_shards = (int32_t)M->devices.size(), e.shard = k;
+  return e;
+}
+
+// Stage: shard k's device current, its precision's records resident, its tile (if it renders into
+// one) and its workspace large enough for tile_pixels
+int prepare_part(rt_multi_scene* M, int k, size_t tile_pixels, bool f32, bool need_tile, RenderCost& cost) {
+  MultiPart& q = M->parts[k];
+  const rt_device_scene* s = M->scenes[M->scene_of[k]];
+  HIP_TRY(hipSetDevice(s->device));
+  const auto tp = Clock::now();
+  if (int r = ensure_precisions(s, prec_bit(f32))) return r;
+  cost.prep_ms = ms_since(tp);
+  if (need_tile)
+    if (int r = grow(&q.d_tile, &q.tile_cap, tile_pixels * 3 * elem_size_of(f32), &cost.allocs)) return r;
+  return grow((void**)&q.ws, &q.ws_cap, workspace_layout(tile_pixels, acc_words_of(f32)).bytes, &cost.allocs);
+}
+
+// Stage: shard k's render (ex: shard_exec's) between its events on its stream; a copied shard's way into the frame
+int enqueue_shard(rt_multi_scene* M, int k, const rt_camera_settings* cs, uint64_t seed, const rt_exec& ex, ShardOut to) {
+  MultiPart& q = M->parts[k];
+  const bool f32 = exec_f32(&ex);
+  const int h = rt_host_image_height(cs);
+  RenderCall c;
+  c.d_out = to == ShardOut::frame ? M->d_gather : q.d_tile;
+  c.ws = q.ws, c.ws_cap = q.ws_cap;
+  c.frame_rows = to == ShardOut::frame ? h : 0;
+  c.lone = true;
+  HIP_TRY(hipEventRecord(q.e0, q.st));
+  if (int r = render_any(M->scenes[M->scene_of[k]], cs, seed, &ex, f32, c, q.st)) return r;
+  HIP_TRY(hipEventRecord(q.e1, q.st));
+  if (to == ShardOut::tile_to_frame) {
+    // shard-local row block b is global block b n + k: one strided copy into the first
+    // device's framebuffer (peer-to-peer over xGMI for another device)
+    const size_t w = (size_t)ex.row_block * cs->image_width * 3 * elem_size_of(f32);
+    HIP_TRY(hipMemcpy2DAsync((char*)M->d_gather + (size_t)k * w, M->devices.size() * w, q.d_tile, w, w,
+                             (size_t)rt_host_shard_rows(h, &ex) / ex.row_block, hipMemcpyDeviceToDevice, q.st));
+  }
+  return RT_OK;
+}
+
+// Stage: the n_values linear values at d_img, or their 8-bit codes (the epilogue, into M->d_codes),
+// to the host buffer in ONE device-to-host copy on `st`
+int enqueue_readback(rt_multi_scene* M, const void* d_img, int64_t n_values, bool f32, int encoding, void* out_host,
+                     hipStream_t st) {
+  if (encoding < 0) {
+    HIP_TRY(hipMemcpyAsync(out_host, d_img, (size_t)n_values * elem_size_of(f32), hipMemcpyDeviceToHost, st));
+    return RT_OK;
+  }
+  if (rt_launch_encode8(d_img, f32 ? 0 : 1, M->d_codes, n_values, encode8_table(encoding), encoding, st))
+    return fail(RT_E_HIP, "encode launch failed: %s", hipGetErrorString(hipGetLastError()));
+  HIP_TRY(hipMemcpyAsync(out_host, M->d_codes, (size_t)n_values, hipMemcpyDeviceToHost, st));
+  return RT_OK;
+}
+
+// Stage: the one place that writes a render's rt_stats (ex: the caller's; t0: the call's start)
+void fill_stats(rt_stats* stats, const rt_multi_scene* M, const rt_camera_settings* cs, const rt_exec* ex,
+                const RenderCost& cost, double build_ms, Clock::time_point t0) {
+  const rt_device_scene* s = M->scenes[0];
+  const bool f32 = exec_f32(ex);
+  std::memset(stats, 0, sizeof *stats);
+  stats->upload_ms = build_ms + M->upload_ms + cost.prep_ms;
+  stats->kernel_ms = cost.kernel_ms;
+  stats->samples = (int64_t)rt_host_shard_rows(rt_host_image_height(cs), ex) * cs->image_width * cs->samples_per_pixel;
+  stats->bvh_nodes = s->host->n_nodes;
+  stats->max_stack = s->host->max_depth;
+  stats->device_allocs = cost.allocs;
+  stats->kernel_block = rt_class_block(!f32, rt_class_of(!f32, s->variant));
+  stats->total_ms = build_ms + ms_since(t0);
+}
+
 // One device (the drop-in's plain rt_render / a one-device scene): everything on the part's
 // stream with ONE host synchronisation — status reset, workspace memset, render, resolve, the 8-bit
 // epilogue, the image's device-to-host copy and the status word's into pinned memory — instead of a
-// thread per shard and a synchronising call for each step (the multi-device path below)
-int render_one(rt_multi_scene* M, const rt_camera_settings* cs, uint64_t seed, const rt_exec& ex, int encoding,
-               void* out_host, rt_stats* stats, double build_ms, int allocs,
-               std::chrono::steady_clock::time_point t0) {
+// thread per shard and a synchronising call for each step (render_many below)
+int render_one(rt_multi_scene* M, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex, void* out_host,
+               RenderCost& cost) {
   MultiPart& q = M->parts[0];
   const rt_device_scene* s = M->scenes[0];
-  const bool f32 = exec_f32(&ex);
-  const int h = rt_host_image_height(cs);
-  const int rows = rt_host_shard_rows(h, &ex);
-  const size_t esize = f32 ? sizeof(float) : sizeof(double);
-  const size_t tile_pixels = (size_t)rows * cs->image_width;
-  HIP_TRY(hipSetDevice(s->device));
-  auto tp = std::chrono::steady_clock::now();
-  if (int r = ensure_precisions(s, f32 ? 1 : 2)) return r;
-  const double prep_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count();
-  if (int r = grow(&q.d_tile, &q.tile_cap, tile_pixels * 3 * esize, &allocs)) return r;
-  const size_t wsb = workspace_bytes(tile_pixels, f32 ? RT_ACC_WORDS(float) : RT_ACC_WORDS(double), nullptr, nullptr);
-  if (int r = grow((void**)&q.ws, &q.ws_cap, wsb, &allocs)) return r;
+  const rt_exec e = shard_exec(M, ex, 0);
+  const bool f32 = exec_f32(ex);
+  const size_t tile_pixels = (size_t)rt_host_shard_rows(rt_host_image_height(cs), ex) * cs->image_width;
+  if (int r = prepare_part(M, 0, tile_pixels, f32, true, cost)) return r;
   // everything below is enqueued on q.st; a failure after the first enqueue synchronises the
   // stream before returning, so no copy into out_host is still in flight when the call returns
   auto enqueue = [&]() -> int {
     HIP_TRY(hipMemsetAsync(s->status, 0, 4 * sizeof(int), q.st));
-    HIP_TRY(hipEventRecord(q.e0, q.st));
-    const int r = f32 ? render_async<float>(s, cs, seed, &ex, (float*)q.d_tile, q.st, q.ws, q.ws_cap, 0, true)
-                      : render_async<double>(s, cs, seed, &ex, (double*)q.d_tile, q.st, q.ws, q.ws_cap, 0, true);
-    if (r) return r;
-    HIP_TRY(hipEventRecord(q.e1, q.st));
-    const void* src = q.d_tile;
-    size_t bytes = tile_pixels * 3 * esize;
-    if (encoding >= 0) {
-      const int64_t nv = (int64_t)tile_pixels * 3;
-      if (rt_launch_encode8(q.d_tile, f32 ? 0 : 1, M->d_codes, nv, encode8_table(encoding), encoding, q.st))
-        return fail(RT_E_HIP, "encode launch failed: %s", hipGetErrorString(hipGetLastError()));
-      src = M->d_codes;
-      bytes = (size_t)nv;
-    }
+    if (int r = enqueue_shard(M, 0, cs, seed, e, ShardOut::tile)) return r;
     // (the image is copied before the status word is read, in the same synchronisation: on
     // RT_E_STACK out_host holds the partial image, include/rt.h)
-    HIP_TRY(hipMemcpyAsync(out_host, src, bytes, hipMemcpyDeviceToHost, q.st));
+    if (int r = enqueue_readback(M, q.d_tile, (int64_t)tile_pixels * 3, f32, exec_encoding(ex), out_host, q.st)) return r;
     HIP_TRY(hipMemcpyAsync(M->h_status, s->status, sizeof(int), hipMemcpyDeviceToHost, q.st));
     return RT_OK;
   };
@@ -532,192 +628,108 @@ int render_one(rt_multi_scene* M, const rt_camera_settings* cs, uint64_t seed, c
   }
   HIP_TRY(hipStreamSynchronize(q.st));
   if (*M->h_status) return fail(RT_E_STACK, "BVH traversal stack overflow");
-  if (stats) {
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, q.e0, q.e1));
-    std::memset(stats, 0, sizeof *stats);
-    stats->upload_ms = build_ms + M->upload_ms + prep_ms;
-    stats->kernel_ms = ms;
-    stats->samples = (int64_t)rows * cs->image_width * cs->samples_per_pixel;
-    stats->bvh_nodes = s->host->n_nodes;
-    stats->max_stack = s->host->max_depth;
-    stats->device_allocs = allocs;
-    stats->kernel_block = rt_class_block(!f32, rt_class_of(!f32, s->variant));
-    stats->total_ms = build_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  HIP_TRY(hipEventElapsedTime(&cost.kernel_ms, q.e0, q.e1));
+  return RT_OK;
+}
+
+// A device list of n > 1 shards (shard k on devices[k]): a host thread per shard prepares, renders
+// and synchronises its part; epilogue and read-back of the gathered frame on st0
+int render_many(rt_multi_scene* M, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex, void* out_host,
+                RenderCost& cost) {
+  const int n = (int)M->devices.size();
+  const bool f32 = exec_f32(ex);
+  const int h = rt_host_image_height(cs);
+  // experiments and tests: shards forced onto the tile + strided-copy path a device without peer
+  // access takes (RT_AMD_COPY_SHARDS: bit k for shard k, -1 every shard), so one GPU exercises it
+  unsigned long long copy_mask = 0;
+  if (const char* e = rt_knob("RT_AMD_COPY_SHARDS")) copy_mask = (unsigned long long)strtoll(e, nullptr, 0);
+  // a stack overflow of an earlier render must not fail this one: clear each device's status word
+  for (size_t j = 0; j < M->scenes.size(); ++j) {
+    const rt_device_scene* s = M->scenes[j];
+    const MultiPart& q = M->parts[std::find(M->scene_of.begin(), M->scene_of.end(), (int)j) - M->scene_of.begin()];
+    if (hipSetDevice(s->device) != hipSuccess || hipMemsetAsync(s->status, 0, 4 * sizeof(int), q.st) != hipSuccess ||
+        hipStreamSynchronize(q.st) != hipSuccess)
+      return fail(RT_E_HIP, "status reset on device %d", s->device);
   }
+  std::vector<RenderCost> costs(n);
+  std::vector<int> rcs(n, RT_OK);
+  std::vector<std::string> errs(n);
+  {
+    std::vector<std::thread> th;
+    for (int k = 0; k < n; ++k)
+      th.emplace_back([&, k] {
+        const MultiPart& q = M->parts[k];
+        const rt_exec e = shard_exec(M, ex, k);
+        // the resolve writes the shard's rows straight into the frame on the first device (over
+        // xGMI from a peer); without peer access, a tile and a strided copy
+        const bool direct = M->peer_ok[M->scene_of[k]] && !((copy_mask >> k) & 1ull);
+        auto run = [&]() -> int {
+          const size_t tile_pixels = (size_t)rt_host_shard_rows(h, &e) * cs->image_width;
+          if (int r = prepare_part(M, k, tile_pixels, f32, !direct, costs[k])) return r;
+          if (int r = enqueue_shard(M, k, cs, seed, e, direct ? ShardOut::frame : ShardOut::tile_to_frame)) return r;
+          HIP_TRY(hipStreamSynchronize(q.st));
+          HIP_TRY(hipEventElapsedTime(&costs[k].kernel_ms, q.e0, q.e1));
+          return RT_OK;
+        };
+        if ((rcs[k] = run())) errs[k] = g_err;
+      });
+    for (auto& t : th) t.join();
+  }
+  for (int k = 0; k < n; ++k) {
+    if (rcs[k]) return fail(rcs[k], "device %d: %s", M->devices[k], errs[k].c_str());
+    cost.prep_ms = std::max(cost.prep_ms, costs[k].prep_ms);
+    cost.kernel_ms = std::max(cost.kernel_ms, costs[k].kernel_ms);
+    cost.allocs += costs[k].allocs;
+  }
+  int status = 0;
+  for (const rt_device_scene* s : M->scenes) {
+    int ps = 0;
+    (void)hipSetDevice(s->device);
+    if (hipMemcpy(&ps, s->status, 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(RT_E_HIP, "status");
+    status |= ps;
+  }
+  if (status) return fail(RT_E_STACK, "BVH traversal stack overflow");
+  (void)hipSetDevice(M->devices[0]);
+  if (int r = enqueue_readback(M, M->d_gather, (int64_t)h * cs->image_width * 3, f32, exec_encoding(ex), out_host, M->st0))
+    return r;
+  if (hipStreamSynchronize(M->st0) != hipSuccess)
+    return fail(RT_E_HIP, "copy back: %s", hipGetErrorString(hipGetLastError()));
   return RT_OK;
 }
 
 // Render the image (device list: shard k of n on devices[k]) or, with one device, the rt_exec
 // shard; gather on the first device; optional 8-bit epilogue there; ONE copy to the host buffer.
-// Every buffer, stream and event is the scene's own (rt_multi_scene), kept across renders.
-int multi_render(rt_multi_scene* M, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex,
-                 void* out_host, rt_stats* stats, double build_ms) {
-  auto t0 = std::chrono::steady_clock::now();
-  if (int rc = check_flags(ex)) return rc;
-  const int h = rt_host_image_height(cs);
-  if (h <= 0 || cs->image_width <= 0) return fail(RT_E_INVALID, "image %dx%d must be non-empty", cs->image_width, h);
+// Every buffer, stream and event is the scene's own (rt_multi_scene), kept across renders.  The
+// frame has passed validate_frame; the devices are the scene's, whatever list ex names.
+int render_sync(rt_multi_scene* M, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex, void* out_host,
+                rt_stats* stats, double build_ms) {
+  const auto t0 = Clock::now();
   const int n = (int)M->devices.size();
   if (n > 1 && ex->n_shards != 1) return fail(RT_E_INVALID, "a device list renders the whole image (n_shards must be 1)");
-  const int rows_out = rt_host_shard_rows(h, ex);  // == h for a device list / a single shard
-  if (rows_out < 0) return fail(RT_E_INVALID, "invalid rt_exec");
-  {  // validate the camera before touching a device
-    KernelParams P;
-    std::string err;
-    int rc = rt_host_make_params(cs, seed, ex, P, err);
-    if (rc) return fail(rc, "%s", err.c_str());
-  }
   std::lock_guard<std::mutex> lock(M->mu);
-  const bool f32 = exec_f32(ex);
-  const int encoding = exec_encoding(ex);
-  const size_t esize = f32 ? sizeof(float) : sizeof(double);
-  const size_t row_bytes = (size_t)cs->image_width * 3 * esize;
-  struct Job {
-    rt_exec ex{};
-    int rows = 0;
-    float ms = 0;
-    int rc = RT_OK;
-    std::string err;
-    double prep_ms = 0;
-    int allocs = 0;
-  };
-  std::vector<Job> jobs(n);
-  // experiments and tests: shards forced onto the tile + strided-copy path a device without peer
-  // access takes (RT_AMD_COPY_SHARDS: bit k for shard k, -1 every shard), so one GPU exercises it
-  unsigned long long copy_mask = 0;
-  if (const char* e = rt_knob("RT_AMD_COPY_SHARDS")) copy_mask = (unsigned long long)strtoll(e, nullptr, 0);
-  for (int k = 0; k < n; ++k) {
-    Job& p = jobs[k];
-    p.ex = *ex;
-    p.ex.n_devices = 0;
-    p.ex.devices = nullptr;
-    p.ex.device = M->devices[k];
-    p.ex.flags &= ~(RT_EXEC_ENCODE8_SRGB | RT_EXEC_ENCODE8_SQRT);  // the tiles are linear; encoded after the gather
-    if (n > 1) {
-      p.ex.n_shards = n;
-      p.ex.shard = k;
-    }
-    p.rows = rt_host_shard_rows(h, &p.ex);
-  }
   // the first device's framebuffer: n shard tiles in global row order (n > 1; padded to equal
-  // tiles), or the single shard's tile itself
-  const int dev0 = M->devices[0];
-  const int rb = ex->row_block;
-  const size_t gather_rows = n > 1 ? (size_t)n * jobs[0].rows : (size_t)rows_out;
-  int allocs = 0;
-  int rc = RT_OK;
-  if (hipSetDevice(dev0) != hipSuccess) rc = fail(RT_E_HIP, "device %d", dev0);
-  if (!rc && n > 1) rc = grow(&M->d_gather, &M->gather_cap, gather_rows * row_bytes, &allocs);
-  if (!rc && encoding >= 0)
-    rc = grow((void**)&M->d_codes, &M->codes_cap, std::max<size_t>(16, gather_rows * cs->image_width * 3), &allocs);
-  if (!rc && n == 1) return render_one(M, cs, seed, jobs[0].ex, encoding, out_host, stats, build_ms, allocs, t0);
-  // a stack overflow of an earlier render must not fail this one: clear each device's status word
-  for (size_t j = 0; j < M->scenes.size() && !rc; ++j) {
-    const rt_device_scene* s = M->scenes[j];
-    const MultiPart& q = M->parts[std::find(M->scene_of.begin(), M->scene_of.end(), (int)j) - M->scene_of.begin()];
-    if (hipSetDevice(s->device) != hipSuccess || hipMemsetAsync(s->status, 0, 4 * sizeof(int), q.st) != hipSuccess ||
-        hipStreamSynchronize(q.st) != hipSuccess)
-      rc = fail(RT_E_HIP, "status reset on device %d", s->device);
-  }
-  if (!rc) {
-    std::vector<std::thread> th;
-    for (int k = 0; k < n; ++k)
-      th.emplace_back([&, k] {
-        Job& p = jobs[k];
-        MultiPart& q = M->parts[k];
-        const rt_device_scene* s = M->scenes[M->scene_of[k]];
-        auto run = [&]() -> int {
-          HIP_TRY(hipSetDevice(s->device));
-          auto tp = std::chrono::steady_clock::now();
-          if (int r = ensure_precisions(s, f32 ? 1 : 2)) return r;
-          p.prep_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count();
-          const size_t tile_pixels = (size_t)p.rows * cs->image_width;
-          // n > 1: the resolve writes the shard's rows straight into the frame on the first device
-          // (over xGMI from a peer); without peer access, a tile and a strided copy
-          const bool direct = n > 1 && M->peer_ok[M->scene_of[k]] && !((copy_mask >> k) & 1ull);
-          if (!direct)
-            if (int r = grow(&q.d_tile, &q.tile_cap, tile_pixels * 3 * esize, &p.allocs)) return r;
-          const size_t wsb = workspace_bytes(tile_pixels, f32 ? RT_ACC_WORDS(float) : RT_ACC_WORDS(double), nullptr, nullptr);
-          if (int r = grow((void**)&q.ws, &q.ws_cap, wsb, &p.allocs)) return r;
-          void* dst = direct ? M->d_gather : q.d_tile;
-          const int frame_rows = direct ? h : 0;
-          HIP_TRY(hipEventRecord(q.e0, q.st));
-          const int r = f32 ? render_async<float>(s, cs, seed, &p.ex, (float*)dst, q.st, q.ws, q.ws_cap, frame_rows, true)
-                            : render_async<double>(s, cs, seed, &p.ex, (double*)dst, q.st, q.ws, q.ws_cap, frame_rows, true);
-          if (r) return r;
-          HIP_TRY(hipEventRecord(q.e1, q.st));
-          if (n > 1 && !direct) {
-            // shard-local row block b is global block b n + k: one strided copy into the first
-            // device's framebuffer (peer-to-peer over xGMI for another device)
-            const size_t w = (size_t)rb * row_bytes;
-            HIP_TRY(hipMemcpy2DAsync((char*)M->d_gather + (size_t)k * w, (size_t)n * w, q.d_tile, w, w,
-                                     (size_t)p.rows / rb, hipMemcpyDeviceToDevice, q.st));
-          }
-          HIP_TRY(hipStreamSynchronize(q.st));
-          HIP_TRY(hipEventElapsedTime(&p.ms, q.e0, q.e1));
-          return RT_OK;
-        };
-        p.rc = run();
-        if (p.rc) p.err = g_err;
-      });
-    for (auto& t : th) t.join();
-    for (int k = 0; k < n && !rc; ++k)
-      if (jobs[k].rc) rc = fail(jobs[k].rc, "device %d: %s", M->devices[k], jobs[k].err.c_str());
-  }
-  for (const Job& p : jobs) allocs += p.allocs;
-  int status = 0;
-  for (size_t j = 0; j < M->scenes.size() && !rc; ++j) {
-    int ps = 0;
-    (void)hipSetDevice(M->scenes[j]->device);
-    if (hipMemcpy(&ps, M->scenes[j]->status, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(RT_E_HIP, "status");
-    status |= ps;
-  }
-  if (!rc && status) rc = fail(RT_E_STACK, "BVH traversal stack overflow");
-  const void* d_img = n > 1 ? M->d_gather : M->parts[0].d_tile;
-  const size_t out_rows = n > 1 ? (size_t)h : (size_t)rows_out;
-  if (!rc) {
-    (void)hipSetDevice(dev0);
-    const void* src = d_img;
-    size_t bytes = out_rows * row_bytes;
-    if (encoding >= 0) {
-      const int64_t nv = (int64_t)out_rows * cs->image_width * 3;
-      if (rt_launch_encode8(d_img, f32 ? 0 : 1, M->d_codes, nv, encode8_table(encoding), encoding, M->st0))
-        rc = fail(RT_E_HIP, "encode launch failed: %s", hipGetErrorString(hipGetLastError()));
-      src = M->d_codes;
-      bytes = (size_t)nv;
-    }
-    if (!rc && (hipMemcpyAsync(out_host, src, bytes, hipMemcpyDeviceToHost, M->st0) != hipSuccess ||
-                hipStreamSynchronize(M->st0) != hipSuccess))
-      rc = fail(RT_E_HIP, "copy back: %s", hipGetErrorString(hipGetLastError()));
-  }
-  if (stats && !rc) {
-    std::memset(stats, 0, sizeof *stats);
-    double prep = 0;
-    float ms = 0;
-    for (const Job& p : jobs) {
-      prep = std::max(prep, p.prep_ms);
-      ms = std::max(ms, p.ms);
-    }
-    stats->upload_ms = build_ms + M->upload_ms + prep;
-    stats->kernel_ms = ms;
-    stats->samples = (int64_t)rows_out * cs->image_width * cs->samples_per_pixel;
-    stats->bvh_nodes = M->scenes[0]->host->n_nodes;
-    stats->max_stack = M->scenes[0]->host->max_depth;
-    stats->device_allocs = allocs;
-    stats->kernel_block = rt_class_block(!f32, rt_class_of(!f32, M->scenes[0]->variant));
-    stats->total_ms = build_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return rc;
+  // tiles), or the single shard's tile itself, which is its part's; the 8-bit codes of either
+  const rt_exec e0 = shard_exec(M, ex, 0);
+  const size_t frame_values = (size_t)n * rt_host_shard_rows(rt_host_image_height(cs), &e0) * cs->image_width * 3;
+  RenderCost cost;
+  if (hipSetDevice(M->devices[0]) != hipSuccess) return fail(RT_E_HIP, "device %d", M->devices[0]);
+  if (n > 1)
+    if (int rc = grow(&M->d_gather, &M->gather_cap, frame_values * elem_size_of(exec_f32(ex)), &cost.allocs)) return rc;
+  if (exec_encoding(ex) >= 0)
+    if (int rc = grow((void**)&M->d_codes, &M->codes_cap, std::max<size_t>(16, frame_values), &cost.allocs)) return rc;
+  if (int rc = n == 1 ? render_one(M, cs, seed, ex, out_host, cost) : render_many(M, cs, seed, ex, out_host, cost)) return rc;
+  if (stats) fill_stats(stats, M, cs, ex, cost, build_ms, t0);
+  return RT_OK;
 }
 
 int build_host(const rt_scene* sc, std::shared_ptr<const HostScene>& out, double& ms) {
-  auto t0 = std::chrono::steady_clock::now();
+  auto t0 = Clock::now();
   auto H = std::make_shared<HostScene>();
   std::string err;
   int rc = rt_host_build_scene(sc, *H, err);
   if (rc) return fail(rc, "%s", err.c_str());
   out = H;
-  ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  ms = ms_since(t0);
   return RT_OK;
 }
 
@@ -839,8 +851,9 @@ int rt_render_async(const rt_device_scene* s, const rt_camera_settings* cs, uint
   if (ex->n_devices != 0) return fail(RT_E_INVALID, "rt_render_async renders on the scene's device (n_devices = 0)");
   if (int rc = check_flags(ex)) return rc;
   if (exec_encoding(ex) >= 0) return fail(RT_E_INVALID, "rt_render_async writes linear RGB (use rt_encode8_async)");
-  if (exec_f32(ex)) return render_async<float>(s, cs, seed, ex, (float*)d_out_rgb, hip_stream);
-  return render_async<double>(s, cs, seed, ex, (double*)d_out_rgb, hip_stream);
+  RenderCall c;  // (no workspace of the caller's: one from the stream-ordered pool)
+  c.d_out = d_out_rgb;
+  return render_any(s, cs, seed, ex, exec_f32(ex), c, hip_stream);
 }
 
 int rt_multi_scene_create(const rt_scene* sc, const int32_t* devices, int32_t n_devices, rt_multi_scene** out) {
@@ -863,8 +876,9 @@ int rt_multi_render(const rt_multi_scene* m, const rt_camera_settings* cs, uint6
                     void* out, rt_stats* stats) {
   if (!m || !cs || !ex || !out) return fail(RT_E_INVALID, "null argument");
   if (ex->n_devices != 0) return fail(RT_E_INVALID, "rt_multi_render renders on the scene's devices (n_devices = 0)");
+  if (int rc = validate_frame(cs, seed, ex)) return rc;
   // the scene's resident buffers are its internal state (the caller's handle stays const)
-  const int rc = multi_render(const_cast<rt_multi_scene*>(m), cs, seed, ex, out, stats, 0.0);
+  const int rc = render_sync(const_cast<rt_multi_scene*>(m), cs, seed, ex, out, stats, 0.0);
   if (!rc && stats) stats->upload_ms += m->build_ms;  // the scene's one-time cost, as rt_render reports it
   return rc;
 }
@@ -872,20 +886,11 @@ int rt_multi_render(const rt_multi_scene* m, const rt_camera_settings* cs, uint6
 int rt_render(const rt_camera_settings* cs, const rt_scene* scene, uint64_t seed, const rt_exec* ex, void* out_rgb,
               rt_stats* stats) {
   if (!cs || !scene || !ex || !out_rgb) return fail(RT_E_INVALID, "null argument");
-  int h = rt_host_image_height(cs);
-  if (h <= 0 || cs->image_width <= 0) return fail(RT_E_INVALID, "image %dx%d must be non-empty", cs->image_width, h);
-  if (rt_host_shard_rows(h, ex) < 0) return fail(RT_E_INVALID, "invalid rt_exec");
-  if (int rc = check_flags(ex)) return rc;
+  if (int rc = validate_frame(cs, seed, ex)) return rc;  // before building or touching a device
   if (ex->n_devices < 0 || ex->n_devices > RT_MAX_DEVICES || (ex->n_devices > 0 && !ex->devices))
     return fail(RT_E_INVALID, "invalid device list (%d devices)", ex->n_devices);
   if (ex->n_devices > 0 && ex->n_shards != 1)
     return fail(RT_E_INVALID, "a device list renders the whole image (n_shards must be 1)");
-  {  // validate the camera before building or touching a device
-    KernelParams P;
-    std::string err;
-    int rc = rt_host_make_params(cs, seed, ex, P, err);
-    if (rc) return fail(rc, "%s", err.c_str());
-  }
   std::shared_ptr<const HostScene> H;
   double build_ms = 0;
   if (int rc = build_host(scene, H, build_ms)) return rc;  // ONE host build, whatever the device count
@@ -893,11 +898,8 @@ int rt_render(const rt_camera_settings* cs, const rt_scene* scene, uint64_t seed
   const int32_t* devs = ex->n_devices > 0 ? ex->devices : &one;
   const int n = ex->n_devices > 0 ? ex->n_devices : 1;
   rt_multi_scene* M = nullptr;
-  if (int rc = multi_create(H, devs, n, exec_f32(ex) ? 1 : 2, &M)) return rc;  // only this call's precision
-  rt_exec e = *ex;
-  e.n_devices = 0;
-  e.devices = nullptr;
-  const int rc = multi_render(M, cs, seed, &e, out_rgb, stats, build_ms);
+  if (int rc = multi_create(H, devs, n, prec_bit(exec_f32(ex)), &M)) return rc;  // only this call's precision
+  const int rc = render_sync(M, cs, seed, ex, out_rgb, stats, build_ms);  // (the list is M's now: shard_exec drops ex's)
   multi_destroy(M);
   return rc;
 }
@@ -918,18 +920,13 @@ int rt_film_create(const rt_device_scene* s, const rt_camera_settings* cs, uint6
   if (!s || !cs || !ex || !out) return fail(RT_E_INVALID, "null argument");
   *out = nullptr;
   if (ex->n_devices != 0) return fail(RT_E_INVALID, "a film lives on the scene's device (n_devices = 0)");
-  if (int rc = check_flags(ex)) return rc;
-  if (exec_encoding(ex) >= 0) return fail(RT_E_INVALID, "a film resolves to linear RGB (use rt_encode8_async)");
   if (cs->n_redirect_targets < 0 || cs->n_redirect_targets > RT_MAX_TARGETS || (cs->n_redirect_targets && !cs->redirect_targets))
     return fail(cs->n_redirect_targets > RT_MAX_TARGETS ? RT_E_UNSUPPORTED : RT_E_INVALID, "invalid redirect targets (%d)",
                 cs->n_redirect_targets);
+  // (the camera's samples_per_pixel is checked too; it is not read afterwards)
+  if (int rc = validate_frame(cs, seed, ex)) return rc;
+  if (exec_encoding(ex) >= 0) return fail(RT_E_INVALID, "a film resolves to linear RGB (use rt_encode8_async)");
   const int h = rt_host_image_height(cs);
-  if (h <= 0 || cs->image_width <= 0) return fail(RT_E_INVALID, "image %dx%d must be non-empty", cs->image_width, h);
-  {  // validate the camera (samples_per_pixel included; it is not read afterwards) before the device
-    KernelParams P;
-    std::string err;
-    if (int rc = rt_host_make_params(cs, seed, ex, P, err)) return fail(rc, "%s", err.c_str());
-  }
   std::unique_ptr<rt_film, void (*)(rt_film*)> f(new rt_film(), film_destroy);
   f->scene = s;
   f->cs = *cs;
@@ -943,25 +940,25 @@ int rt_film_create(const rt_device_scene* s, const rt_camera_settings* cs, uint6
   f->width = cs->image_width;
   f->height = h;
   f->rows = rt_host_shard_rows(h, ex);
-  f->acc_words = f->f32 ? RT_ACC_WORDS(float) : RT_ACC_WORDS(double);
+  f->acc_words = acc_words_of(f->f32);
   f->n_pixels = (size_t)f->rows * f->width;
-  if (int rc = ensure_precisions(s, f->f32 ? 1 : 2)) return rc;
+  if (int rc = ensure_precisions(s, prec_bit(f->f32))) return rc;
   auto pad = [](size_t b) { return (b + 16 + 255) & ~(size_t)255; };  // >= 16 bytes of slack, 256-byte parts
   f->total_bytes = pad(film_sums_bytes(f.get()));
   f->flag_bytes = pad(f->n_pixels * sizeof(unsigned));
   f->q_bytes = pad(f->n_pixels * sizeof(double));
   f->state_span = f->total_bytes + f->flag_bytes + f->q_bytes;
-  f->ws_bytes = workspace_bytes(f->n_pixels, f->acc_words, nullptr, nullptr);
-  const size_t tile_bytes = pad(f->n_pixels * 3 * (f->f32 ? sizeof(float) : sizeof(double)));
+  f->ws_lay = workspace_layout(f->n_pixels, f->acc_words);
+  const size_t tile_bytes = pad(f->n_pixels * 3 * elem_size_of(f->f32));
   const size_t blocks = (size_t)rt_film_blocks((long long)f->n_pixels);
   const size_t part_bytes = pad(blocks * sizeof(double)) + pad(blocks * sizeof(int));
   HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipMalloc((void**)&f->mem, f->state_span + f->ws_bytes + tile_bytes + part_bytes));
+  HIP_TRY(hipMalloc((void**)&f->mem, f->state_span + f->ws_lay.bytes + tile_bytes + part_bytes));
   char* p = f->mem;
   f->total = (unsigned long long*)p, p += f->total_bytes;
   f->flags = (unsigned int*)p, p += f->flag_bytes;
   f->q = (double*)p, p += f->q_bytes;
-  f->ws = p, p += f->ws_bytes;
+  f->ws = p, p += f->ws_lay.bytes;
   f->tile = p, p += tile_bytes;
   f->partial_sum = (double*)p, p += pad(blocks * sizeof(double));
   f->partial_cnt = (int*)p;
@@ -994,17 +991,15 @@ int rt_film_add(rt_film* f, int32_t n_samples, void* hip_stream) {
     return fail(RT_E_INVALID, "a film holds at most 2^24 samples per pixel (%lld + %d)", (long long)f->samples, n_samples);
   rt_camera_settings cs = f->cs;
   cs.samples_per_pixel = n_samples;
-  const int s0 = (int)f->samples;
-  const int rc = f->f32 ? render_async<float>(f->scene, &cs, f->seed, &f->ex, (float*)nullptr, hip_stream, f->ws,
-                                              f->ws_bytes, 0, true, s0, false)
-                        : render_async<double>(f->scene, &cs, f->seed, &f->ex, (double*)nullptr, hip_stream, f->ws,
-                                               f->ws_bytes, 0, true, s0, false);
-  if (rc) return rc;
+  RenderCall c;  // samples [N, N + n) summed into the film's workspace, no mean
+  c.ws = f->ws, c.ws_cap = f->ws_lay.bytes;
+  c.lone = true;
+  c.sample0 = (int)f->samples;
+  c.resolve = false;
+  if (int rc = render_any(f->scene, &cs, f->seed, &f->ex, f->f32, c, hip_stream)) return rc;
   f->last = (hipStream_t)hip_stream;
-  size_t off_flag = 0;
-  (void)workspace_bytes(f->n_pixels, f->acc_words, &off_flag, nullptr);
   if (rt_film_launch_merge(f->total, f->flags, f->q, (const unsigned long long*)f->ws,
-                           (const unsigned int*)(f->ws + off_flag), (long long)f->n_pixels, f->acc_words, n_samples,
+                           (const unsigned int*)(f->ws + f->ws_lay.off_flag), (long long)f->n_pixels, f->acc_words, n_samples,
                            hip_stream))
     return fail(RT_E_HIP, "merge launch failed: %s", hipGetErrorString(hipGetLastError()));
   f->samples += n_samples;
@@ -1021,7 +1016,7 @@ int rt_film_read(const rt_film* f, void* host_out_rgb) {
   if (!f || !host_out_rgb) return fail(RT_E_INVALID, "null argument");
   std::lock_guard<std::mutex> lock(const_cast<rt_film*>(f)->mu);  // (the tile is the film's scratch)
   if (int rc = film_resolve_any(f, f->tile, f->last)) return rc;
-  const size_t bytes = f->n_pixels * 3 * (f->f32 ? sizeof(float) : sizeof(double));
+  const size_t bytes = f->n_pixels * 3 * elem_size_of(f->f32);
   int status = 0;
   HIP_TRY(hipMemcpyAsync(host_out_rgb, f->tile, bytes, hipMemcpyDeviceToHost, f->last));
   HIP_TRY(hipMemcpyAsync(&status, f->scene->status, sizeof(int), hipMemcpyDeviceToHost, f->last));

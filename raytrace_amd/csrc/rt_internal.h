@@ -342,7 +342,7 @@ struct KernelParamsT {
   // resolve target: 0 = `out` holds the shard's tile (tile_rows x width, shard-compact); otherwise
   // `out` is the WHOLE frame of out_frame_rows rows (a multi-device scene's gather buffer on the
   // first device, written across xGMI by peer devices) and the resolve puts each tile row at its
-  // global row, so no separate gather copy is needed (rt_api.hip multi_render)
+  // global row, so no separate gather copy is needed (rt_api.hip render_many)
   int out_frame_rows;
   FastDiv div_width, div_block;  // image width, row block
   // first sample index of this launch: the items cover samples [sample0, sample0 + cam.spp) of

@@ -511,12 +511,24 @@ def test_multi_device_scene_allocates_once(gpu, precision):
     assert st[2]["device_allocs"] == 1, st  # the 8-bit buffer, once
     assert st[3]["device_allocs"] > 0 and again["device_allocs"] == 0, (st, again)
     m.close()
+    # the same sequence on one device (rt_api.hip render_one): its tile and its workspace, no gather
+    m = R.MultiDeviceScene(world, [0])
+    st = [{} for _ in range(6)]
+    np.testing.assert_array_equal(m.render(cs, seed, precision=precision, stats=st[0]), a)
+    np.testing.assert_array_equal(m.render(cs, seed, precision=precision, stats=st[1]), a)
+    np.testing.assert_array_equal(m.render(cs, seed, precision=precision, encode="sqrt", stats=st[2]), R.encode8(a, "sqrt"))
+    np.testing.assert_array_equal(m.render(cs, seed, precision=precision, encode="sqrt", stats=st[3]), R.encode8(a, "sqrt"))
+    np.testing.assert_array_equal(m.render(big, seed, precision=precision, stats=st[4]), b)
+    np.testing.assert_array_equal(m.render(big, seed, precision=precision, stats=st[5]), b)
+    m.close()
+    assert [s["device_allocs"] for s in st[:4]] == [2, 0, 1, 0], st  # tile and workspace; nothing; the 8-bit buffer; nothing
+    assert st[4]["device_allocs"] > 0 and st[5]["device_allocs"] == 0, st
 
 
 @pytest.mark.parametrize("precision", ["f64", "f32"])
 def test_multi_device_copy_path(knobs, gpu, monkeypatch, precision):
     """The path of a shard whose device has no peer access to the first one (rt_api.hip
-    multi_render: its own tile, then one strided hipMemcpy2DAsync into the frame), forced on one GPU
+    enqueue_shard: its own tile, then one strided hipMemcpy2DAsync into the frame), forced on one GPU
     with RT_AMD_COPY_SHARDS (bit k: shard k): every shard copied, and copied and direct shards
     writing the same frame.  Bit-identical to the one-device render, linear and encoded; the first
     render allocates the workspaces, the copied shards' tiles and the frame, the next ones nothing."""
@@ -541,7 +553,7 @@ def test_multi_device_copy_path(knobs, gpu, monkeypatch, precision):
 @pytest.mark.parametrize("precision", ["f64", "f32"])
 def test_multi_device_distinct_gpus(gpu, precision):
     """A device list over DISTINCT GPUs: each peer device's resolve writes its rows straight into the
-    first device's frame over xGMI (rt_api.hip multi_render).  [0, 1] and [0, 1, 0, 1], linear in
+    first device's frame over xGMI (rt_api.hip render_many).  [0, 1] and [0, 1, 0, 1], linear in
     both precisions and 8-bit, rendered twice (the resident buffers re-used across devices), each
     bit-identical to the one-device render.  Needs two GPUs: skipped on the one-GPU box, runs on the
     driver's multi-GPU node."""
