@@ -41,6 +41,8 @@ module Graphics.Ray.Device
   , renderOnDevice, deviceCount
     -- * Progressive rendering on a film (rt.h rt_film_*): stop when the noise is low enough
   , raytraceUntil, renderUntilOnDevice
+    -- * ... and a denoised preview of it (rt.h rt_denoise_*)
+  , raytraceDenoised, renderDenoisedOnDevice
     -- * 8-bit output encoded on the device (writeImage / writeImageSqrt of a render, Ray.hs:248-260)
   , Encoding(..), renderImage8, raytraceToFile
     -- * Geometry (Geometry.hs:5-16)
@@ -564,6 +566,14 @@ foreign import ccall safe "rt_film_read"
   c_rt_film_read :: Ptr () -> Ptr () -> IO CInt
 foreign import ccall safe "rt_film_noise"
   c_rt_film_noise :: Ptr () -> Ptr CFloat -> Ptr CDouble -> IO CInt
+-- the film's first-hit features and its denoised image (rt.h rt_denoise_*; a null parameter
+-- pointer takes the library's defaults)
+foreign import ccall safe "rt_denoise_features"
+  c_rt_denoise_features :: Ptr () -> Int32 -> Ptr () -> IO CInt
+foreign import ccall safe "rt_denoise_albedo"
+  c_rt_denoise_albedo :: Ptr () -> Int32 -> Ptr () -> IO CInt
+foreign import ccall safe "rt_denoise_film_read"
+  c_rt_denoise_film_read :: Ptr () -> Ptr () -> Ptr () -> IO CInt
 
 -- Struct layouts of include/rt.h (x86-64).  tests/test_abi.py checks every `-- LAYOUT` line
 -- against the C compiler's offsetof / sizeof.
@@ -942,7 +952,21 @@ libraryError rc = Left . LibraryError (fromIntegral rc) <$> (c_rt_last_error >>=
 -- sample count.  The film lives on the first device of 'doDevices' (device 0 by default).
 renderUntilOnDevice :: DeviceOptions -> R.CameraSettings -> Geometry m Material -> StdGen -> Double -> Int
                     -> IO (Either RenderError (A.Matrix A.S Color, Int))
-renderUntilOnDevice opts settings world gen target batch =
+renderUntilOnDevice = renderUntilWith filmImage
+
+-- | 'renderUntilOnDevice' whose image is the film's denoised one (rt_denoise_features over 8
+-- samples, rt_denoise_albedo over 64, then rt_denoise_film_read with the library's default parameters): the preview of a
+-- frame stopped early.  The variance estimate needs two passes, so cs_samplesPerPixel must exceed
+-- @batch@ (the library's RT_E_INVALID otherwise); one device, one shard.
+renderDenoisedOnDevice :: DeviceOptions -> R.CameraSettings -> Geometry m Material -> StdGen -> Double -> Int
+                       -> IO (Either RenderError (A.Matrix A.S Color, Int))
+renderDenoisedOnDevice = renderUntilWith filmDenoised
+
+-- | The passes of 'renderUntilOnDevice', then @readout precision film height width@.
+renderUntilWith :: (Precision -> Ptr () -> Int -> Int -> IO (Either RenderError (A.Matrix A.S Color)))
+                -> DeviceOptions -> R.CameraSettings -> Geometry m Material -> StdGen -> Double -> Int
+                -> IO (Either RenderError (A.Matrix A.S Color, Int))
+renderUntilWith readout opts settings world gen target batch =
   case (geoDesc world, reifyBackground (R.cs_background settings)) of
     (Just desc, Just bg) -> do
       tagged <- tagShared desc
@@ -967,7 +991,7 @@ renderUntilOnDevice opts settings world gen target batch =
                       done <- filmPasses film (R.cs_samplesPerPixel settings) target (max 1 batch)
                       out <- case done of
                         Left e -> pure (Left e)
-                        Right spp -> fmap (\img -> (img, spp)) <$> filmImage (doPrecision opts) film h w
+                        Right spp -> fmap (\img -> (img, spp)) <$> readout (doPrecision opts) film h w
                       _ <- c_rt_film_destroy film
                       pure out
                     _ <- c_rt_scene_destroy scene
@@ -996,17 +1020,30 @@ filmPasses film maxSpp target batch = alloca $ \pnoise -> go pnoise 0 (0 :: Int)
 
 -- | The film's image (rt_film_read) as a storable matrix; FP32 films are widened to Double.
 filmImage :: Precision -> Ptr () -> Int -> Int -> IO (Either RenderError (A.Matrix A.S Color))
-filmImage prec film h w = do
+filmImage = filmReadWith c_rt_film_read
+
+-- | The film's denoised image: its features over 8 samples, its remodulation albedo over 64, then
+-- rt_denoise_film_read.
+filmDenoised :: Precision -> Ptr () -> Int -> Int -> IO (Either RenderError (A.Matrix A.S Color))
+filmDenoised prec film h w = do
+  rc0 <- c_rt_denoise_features film 8 nullPtr
+  rc <- if rc0 /= 0 then pure rc0 else c_rt_denoise_albedo film 64 nullPtr
+  if rc /= 0 then libraryError rc else filmReadWith (\f out -> c_rt_denoise_film_read f nullPtr out) prec film h w
+
+-- | A film read-out (@film -> host buffer -> status@) as a storable matrix.
+filmReadWith :: (Ptr () -> Ptr () -> IO CInt) -> Precision -> Ptr () -> Int -> Int
+             -> IO (Either RenderError (A.Matrix A.S Color))
+filmReadWith readFilm prec film h w = do
   let n = 3 * h * w
       asColors fp = A.resize' (A.Sz2 h w) (AU.unsafeArrayFromForeignPtr0 A.Par (fp :: ForeignPtr Color) (A.Sz1 (h * w)))
   fp <- mallocForeignPtrArray n :: IO (ForeignPtr CDouble)
   if prec == Binary64
     then do
-      rc <- withForeignPtr fp $ \out -> c_rt_film_read film (castPtr out)
+      rc <- withForeignPtr fp $ \out -> readFilm film (castPtr out)
       if rc /= 0 then libraryError rc else pure (Right (asColors (castForeignPtr fp)))
     else do
       fp32 <- mallocForeignPtrArray n :: IO (ForeignPtr CFloat)
-      rc <- withForeignPtr fp32 $ \out -> c_rt_film_read film (castPtr out)
+      rc <- withForeignPtr fp32 $ \out -> readFilm film (castPtr out)
       if rc /= 0 then libraryError rc else do
         withForeignPtr fp32 $ \src -> withForeignPtr fp $ \dst ->
           forM_ [0 .. n - 1] $ \i -> peekElemOff src i >>= pokeElemOff dst i . realToFrac
@@ -1025,3 +1062,16 @@ raytraceUntil settings world gen noise batch =
     Left e | fallback e -> (R.raytrace settings (toReferenceRandom world) gen, R.cs_samplesPerPixel settings)
            | otherwise -> error ("Graphics.Ray.Device.raytraceUntil: the film failed: " ++ show e)
 {-# NOINLINE raytraceUntil #-}
+
+-- | 'raytraceUntil' whose image is denoised for a preview (rt.h rt_denoise_*: the film's mean
+-- divided by the first-hit albedo, filtered under normal, depth and variance-scaled luminance
+-- weights, multiplied back).  cs_samplesPerPixel must exceed @batch@ (two passes).  The fallback
+-- rules are 'raytrace''s; the CPU path has no denoiser and returns the plain render.
+raytraceDenoised :: R.ToRandom m => R.CameraSettings -> Geometry m Material -> StdGen -> Double -> Int
+                 -> (A.Matrix A.D Color, Int)
+raytraceDenoised settings world gen noise batch =
+  case unsafePerformIO (renderDenoisedOnDevice defaultDeviceOptions settings world gen noise batch) of
+    Right (img, spp) -> (A.delay img, spp)
+    Left e | fallback e -> (R.raytrace settings (toReferenceRandom world) gen, R.cs_samplesPerPixel settings)
+           | otherwise -> error ("Graphics.Ray.Device.raytraceDenoised: the film failed: " ++ show e)
+{-# NOINLINE raytraceDenoised #-}

@@ -361,6 +361,61 @@ int rt_film_state_bytes(const rt_film* f, int64_t* bytes);
 int rt_film_save(const rt_film* f, void* host_buf, int64_t cap);
 int rt_film_load(rt_film* f, const void* host_buf, int64_t bytes);
 
+/* First-hit feature buffers and a variance-guided denoiser for a film's preview.
+ *
+ * rt_denoise_features: for samples [0, n_feat) of every tile pixel (1 <= n_feat <= 4096), trace the
+ *   primary ray the render uses for that sample (same Philox key and events) to its first event,
+ *   found as the render's first segment finds it (surfaces, then the segment's medium events), and
+ *   add 8 int64 words per pixel: albedo RGB (the hit material's texture; 1 for dielectric, 0 for
+ *   pitchBlack; the phase material's texture in a medium; the background on a miss), the unit
+ *   normal facing the ray (0 in a medium and on a miss) and the hit distance — each in units of
+ *   2^-32, as the render's sums — and the number of samples that hit; a binary64 film adds 8 more
+ *   words, the next 32 bits of each of those sums (the last unused), as its colour sums have.
+ *   Integer sums: identical from run to run.  The buffers are allocated on the first call (a film that never asks
+ *   allocates nothing) and are a function of scene, camera and seed: rt_film_add / reset / load do
+ *   not touch them, and they are not part of rt_film_save's state.  Asynchronous on hip_stream.
+ * rt_denoise_features_read: the words (tile pixels x 8 int64; x 16 for a binary64 film) and their
+ *   n_feat to the host, behind
+ *   the film's last stream; RT_E_INVALID before rt_denoise_features.
+ * rt_denoise_albedo: the same pass over samples [0, n_albedo) into a second buffer of the same
+ *   layout (allocated on its first call), of which the filter reads the albedo alone: it divides the
+ *   colour by the albedo of rt_denoise_features' samples — the film's own first samples, whose
+ *   coverage noise at an emitter's or a texture's edge the two then share and the quotient loses —
+ *   and multiplies the filtered quotient by this better estimate of the same albedo.  Optional:
+ *   without it the filter multiplies by what it divided by.  64 samples cost eight feature passes
+ *   of 8, once per film: like the features, the buffer does not change as samples are added.
+ *   n_albedo = 0 drops it again.
+ * rt_denoise_albedo_read: rt_denoise_albedo's words, as rt_denoise_features_read.
+ * rt_denoise_film: enqueue the filtered image into d_out_rgb (as rt_film_resolve's).  The mean
+ *   colour (the sums' high words) is divided by the albedo, filtered by `levels` passes of a 5 x 5
+ *   a-trous kernel at steps 1, 2, 4, ... whose taps are weighted by normal, depth, albedo and — scaled
+ *   by the film's variance estimate — luminance similarity, and multiplied by the albedo again
+ *   (DESIGN.md "Denoiser": the exact operation sequence, binary64 whatever the film's precision;
+ *   raytrace_amd.denoise.denoise_reference restates it in numpy bit for bit).  NaN-flagged pixels
+ *   stay NaN and are not read by their neighbours.  RT_E_INVALID unless the film holds two passes and
+ *   its features have been computed, for levels outside 1..8, k outside 0..16 or a sigma / eps that
+ *   is not positive; RT_E_UNSUPPORTED for a film of n_shards > 1 (its rows are interleaved with
+ *   other shards', and the filter needs a pixel's neighbours).  The working buffers are allocated on
+ *   the first call and kept.  p == NULL: rt_denoise_default_params.
+ * rt_denoise_film_read: the same into a host buffer, synchronous (as rt_film_read). */
+typedef struct rt_denoise_params {
+  int32_t levels;          /* 1..8 filter passes; pass i steps 2^i pixels (default 5) */
+  int32_t k;               /* normal weight: cosine to the power 2^k (default 5) */
+  double sigma_z;          /* relative depth difference at which the depth weight is 1/2 (0.1) */
+  double sigma_l;          /* luminance difference in standard deviations at which its weight is 1/2 (4) */
+  double sigma_a;          /* relative albedo difference at which the albedo weight is 1/2 (0.1) */
+  double eps_n;            /* |mean normal|^2 below this: a featureless pixel (1e-6) */
+  double eps_z;            /* floor of the depth scale (1e-6) */
+  double eps_l;            /* added to the luminance weight's variance term (1e-10) */
+} rt_denoise_params;
+int rt_denoise_default_params(rt_denoise_params* p);
+int rt_denoise_features(rt_film* f, int32_t n_feat, void* hip_stream);
+int rt_denoise_albedo(rt_film* f, int32_t n_albedo, void* hip_stream);
+int rt_denoise_features_read(const rt_film* f, int64_t* host_words, int32_t* n_feat);
+int rt_denoise_albedo_read(const rt_film* f, int64_t* host_words, int32_t* n_albedo);
+int rt_denoise_film(rt_film* f, const rt_denoise_params* p, void* d_out_rgb, void* hip_stream);
+int rt_denoise_film_read(rt_film* f, const rt_denoise_params* p, void* host_out_rgb);
+
 #ifdef __cplusplus
 }
 #endif

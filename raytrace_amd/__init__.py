@@ -9,6 +9,7 @@ from .camera import (Background, CameraSettings, constBackground, defaultCameraS
                      lerpYBackground, sky)
 from .core import (V3, X, Y, Z, StdGen, allCorners, boxHull, boxJoin, component, degrees, fromCorners, infinity,
                    inInterval, longestDim, midpoint, mkStdGen, padBox, padInterval, reflect, shiftBox)
+from .denoise import denoise_reference, emitter_twin
 from .errors import RtDeviceError, RtError, RtInvalid, RtUnsupported
 from .film import Film, noise_from_sums, raytrace_until
 from .geometry import (M44, Mesh, ObjParseError, boundingBox, bvhNode, bvhTree, constantMedium, cuboid, group,

@@ -21,7 +21,9 @@ EXPORTED = ["rt_abi_version", "rt_last_error", "rt_device_count", "rt_image_heig
             "rt_scene_create", "rt_scene_destroy", "rt_scene_stats", "rt_render_async", "rt_encode8_async",
             "rt_multi_scene_create", "rt_multi_scene_destroy", "rt_multi_render",
             "rt_film_create", "rt_film_destroy", "rt_film_reset", "rt_film_add", "rt_film_resolve", "rt_film_read",
-            "rt_film_noise", "rt_film_get_info", "rt_film_state_bytes", "rt_film_save", "rt_film_load"]
+            "rt_film_noise", "rt_film_get_info", "rt_film_state_bytes", "rt_film_save", "rt_film_load",
+            "rt_denoise_default_params", "rt_denoise_features", "rt_denoise_albedo", "rt_denoise_features_read", "rt_denoise_albedo_read", "rt_denoise_film",
+            "rt_denoise_film_read"]
 
 
 class RtRedirectTarget(ctypes.Structure):
@@ -82,6 +84,12 @@ class RtFilmInfo(ctypes.Structure):
                 ("rows", ctypes.c_int32), ("nan_pixels", ctypes.c_int32), ("f32", ctypes.c_int32)]
 
 
+class RtDenoiseParams(ctypes.Structure):
+    _fields_ = [("levels", ctypes.c_int32), ("k", ctypes.c_int32), ("sigma_z", ctypes.c_double),
+                ("sigma_l", ctypes.c_double), ("sigma_a", ctypes.c_double), ("eps_n", ctypes.c_double), ("eps_z", ctypes.c_double),
+                ("eps_l", ctypes.c_double)]
+
+
 _lib = None
 
 
@@ -127,6 +135,13 @@ def load():
     L.rt_film_state_bytes.argtypes = [P, ctypes.POINTER(ctypes.c_int64)]
     L.rt_film_save.argtypes = [P, P, ctypes.c_int64]
     L.rt_film_load.argtypes = [P, P, ctypes.c_int64]
+    L.rt_denoise_default_params.argtypes = [ctypes.POINTER(RtDenoiseParams)]
+    L.rt_denoise_features.argtypes = [P, ctypes.c_int32, P]
+    L.rt_denoise_albedo.argtypes = [P, ctypes.c_int32, P]
+    L.rt_denoise_features_read.argtypes = [P, P, ctypes.POINTER(ctypes.c_int32)]
+    L.rt_denoise_albedo_read.argtypes = [P, P, ctypes.POINTER(ctypes.c_int32)]
+    L.rt_denoise_film.argtypes = [P, ctypes.POINTER(RtDenoiseParams), P, P]
+    L.rt_denoise_film_read.argtypes = [P, ctypes.POINTER(RtDenoiseParams), P]
     for name in EXPORTED:
         getattr(L, name)
     if L.rt_abi_version() != ABI_VERSION:

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/rt.h"
+#include "rt_denoise.h"
 #include "rt_film.h"
 #include "rt_internal.h"
 #include "rt_kernel_class.h"
@@ -201,6 +202,13 @@ struct rt_film {
   size_t total_bytes = 0, flag_bytes = 0, q_bytes = 0, state_span = 0;  // (padded; total, flags, q are contiguous)
   hipStream_t last = nullptr;  // the stream of the last enqueue: the synchronous calls run behind it
   std::mutex mu;
+  // first-hit features and the denoiser's planes (rt_denoise.h): allocations of their own, made by
+  // the first rt_denoise_features / rt_denoise_film and kept; not part of the saved state
+  unsigned long long* feat = nullptr;  // rt_feat_words(binary64) int64 per tile pixel
+  int feat_samples = 0;                // n_feat of the words in `feat` (0: none yet)
+  unsigned long long* feat2 = nullptr; // the remodulation albedo's feature words (rt_denoise_albedo)
+  int albedo_samples = 0;              // ... and their sample count (0: none)
+  double* dn_mem = nullptr;            // ev[2][4] and guide[8] planes of n_pixels doubles
 };
 
 namespace {
@@ -763,6 +771,9 @@ void film_destroy(rt_film* f) {
     (void)hipSetDevice(f->scene->device);
     if (f->last) (void)hipStreamSynchronize(f->last);
     (void)hipFree(f->mem);
+    (void)hipFree(f->feat);
+    (void)hipFree(f->feat2);
+    (void)hipFree(f->dn_mem);
   }
   delete f;
 }
@@ -785,6 +796,60 @@ int film_resolve_any(const rt_film* f, void* d_out, hipStream_t st) {
   if (f->samples <= 0) return fail(RT_E_INVALID, "the film holds no samples");
   HIP_TRY(hipSetDevice(f->scene->device));
   return f->f32 ? film_resolve<float>(f, d_out, st) : film_resolve<double>(f, d_out, st);
+}
+
+// ---- first-hit features and the denoiser (rt_denoise.h, rt_features.h)
+
+// samples [0, n_feat) of every tile pixel into the zeroed feature words `feat`
+template <class R>
+int film_features(rt_film* f, unsigned long long* feat, int n_feat, hipStream_t st) {
+  const rt_device_scene* s = f->scene;
+  if (int rc = ensure_precision<R>(s)) return rc;
+  LaunchInputs L;
+  L.resident_lanes = 4096;  // (the work plan is the render's; the feature kernel has its own)
+  L.lds_nodes = 0;          // no staged nodes: every node from memory
+  rt_camera_settings cs = f->cs;
+  cs.samples_per_pixel = n_feat;
+  KernelParamsT<R> P;
+  std::string err;
+  if (int rc = rt_host_render_params(*s->host, s->variant, s->arrays<R>().rec, &cs, f->seed, &f->ex, L, P, err))
+    return fail(rc, "%s", err.c_str());
+  P.status = s->status;
+  HIP_TRY(hipMemsetAsync(feat, 0, f->n_pixels * rt_feat_words(!f->f32) * sizeof(long long), st));
+  if (rt_launch_features(P, s->variant, feat, n_feat, st))
+    return fail(RT_E_HIP, "feature launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return RT_OK;
+}
+
+// the checks of rt_denoise_film / _read that need no device; p: the parameters in effect
+int denoise_check(const rt_film* f, const rt_denoise_params* p) {
+  if (!rt_dn_params_ok(p))
+    return fail(RT_E_INVALID, "denoise parameters: levels 1..8 (%d), k 0..16 (%d), sigma and eps positive", p->levels, p->k);
+  if (f->ex.n_shards > 1)
+    return fail(RT_E_UNSUPPORTED, "a film of %d shards holds interleaved rows: the filter needs a pixel's neighbours",
+                f->ex.n_shards);
+  if (f->passes < 2) return fail(RT_E_INVALID, "the denoiser's variance needs two passes (the film has %d)", f->passes);
+  if (f->feat_samples <= 0) return fail(RT_E_INVALID, "the film's features have not been computed (rt_denoise_features)");
+  return RT_OK;
+}
+
+// prepare, one launch per level over the two ev buffers, finish
+int film_denoise(rt_film* f, const rt_denoise_params* p, void* d_out, hipStream_t st) {
+  HIP_TRY(hipSetDevice(f->scene->device));
+  const size_t n = f->n_pixels;
+  if (!f->dn_mem)
+    HIP_TRY(hipMalloc((void**)&f->dn_mem, (2 * RT_DN_EV_PLANES + RT_DN_GUIDE_PLANES) * n * sizeof(double)));
+  double* ev[2] = {f->dn_mem, f->dn_mem + RT_DN_EV_PLANES * n};
+  double* guide = f->dn_mem + 2 * RT_DN_EV_PLANES * n;
+  int rc = rt_denoise_launch_prepare(f->total, f->q, (const long long*)f->feat, ev[0], guide, (long long)n, f->acc_words,
+                                     f->samples, f->passes, f->feat_samples,
+                                     f->albedo_samples > 0 ? (const long long*)f->feat2 : nullptr, f->albedo_samples, st);
+  int cur = 0;
+  for (int i = 0; i < p->levels && !rc; ++i, cur ^= 1)
+    rc = rt_denoise_launch_level(ev[cur], ev[cur ^ 1], guide, f->flags, p, f->width, f->height, 1 << i, st);
+  if (!rc) rc = rt_denoise_launch_finish(ev[cur], guide, f->flags, d_out, f->f32, (long long)n, st);
+  if (rc) return fail(RT_E_HIP, "denoise launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return RT_OK;
 }
 
 }  // namespace
@@ -1117,6 +1182,101 @@ int rt_film_load(rt_film* f, const void* host_buf, int64_t bytes) {
   HIP_TRY(hipStreamSynchronize(f->last));
   f->samples = h.samples;
   f->passes = h.passes;
+  return RT_OK;
+}
+
+// ---- first-hit features and the denoiser
+
+int rt_denoise_default_params(rt_denoise_params* p) {
+  if (!p) return fail(RT_E_INVALID, "null argument");
+  rt_dn_defaults(p);
+  return RT_OK;
+}
+
+int rt_denoise_features(rt_film* f, int32_t n_feat, void* hip_stream) {
+  if (!f) return fail(RT_E_INVALID, "null argument");
+  if (n_feat < 1 || n_feat > 4096) return fail(RT_E_INVALID, "1 to 4096 feature samples per pixel (%d)", n_feat);
+  std::lock_guard<std::mutex> lock(f->mu);
+  HIP_TRY(hipSetDevice(f->scene->device));
+  if (!f->feat) HIP_TRY(hipMalloc((void**)&f->feat, f->n_pixels * rt_feat_words(!f->f32) * sizeof(long long)));
+  f->feat_samples = 0;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (int rc = f->f32 ? film_features<float>(f, f->feat, n_feat, st) : film_features<double>(f, f->feat, n_feat, st)) return rc;
+  f->feat_samples = n_feat;
+  f->last = st;
+  return RT_OK;
+}
+
+int rt_denoise_albedo(rt_film* f, int32_t n_albedo, void* hip_stream) {
+  if (!f) return fail(RT_E_INVALID, "null argument");
+  if (n_albedo < 0 || n_albedo > 4096) return fail(RT_E_INVALID, "0 to 4096 albedo samples per pixel (%d)", n_albedo);
+  std::lock_guard<std::mutex> lock(f->mu);
+  if (n_albedo == 0) {  // back to multiplying by the features' own albedo
+    f->albedo_samples = 0;
+    return RT_OK;
+  }
+  HIP_TRY(hipSetDevice(f->scene->device));
+  if (!f->feat2) HIP_TRY(hipMalloc((void**)&f->feat2, f->n_pixels * rt_feat_words(!f->f32) * sizeof(long long)));
+  f->albedo_samples = 0;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (int rc = f->f32 ? film_features<float>(f, f->feat2, n_albedo, st) : film_features<double>(f, f->feat2, n_albedo, st))
+    return rc;
+  f->albedo_samples = n_albedo;
+  f->last = st;
+  return RT_OK;
+}
+
+namespace {
+// a feature buffer's words to the host, behind the film's last stream
+int features_read(const rt_film* f, const unsigned long long* words, int samples, const char* what, int64_t* host_words,
+                  int32_t* n_out) {
+  if (!f || !host_words || !n_out) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(const_cast<rt_film*>(f)->mu);
+  if (samples <= 0) return fail(RT_E_INVALID, "the film's features have not been computed (%s)", what);
+  int status = 0;
+  HIP_TRY(hipSetDevice(f->scene->device));
+  HIP_TRY(hipMemcpyAsync(host_words, words, f->n_pixels * rt_feat_words(!f->f32) * sizeof(long long), hipMemcpyDeviceToHost,
+                         f->last));
+  HIP_TRY(hipMemcpyAsync(&status, f->scene->status, sizeof(int), hipMemcpyDeviceToHost, f->last));
+  HIP_TRY(hipStreamSynchronize(f->last));
+  *n_out = samples;
+  if (status) return fail(RT_E_STACK, "BVH traversal stack overflow");
+  return RT_OK;
+}
+}  // namespace
+
+int rt_denoise_features_read(const rt_film* f, int64_t* host_words, int32_t* n_feat) {
+  if (!f) return fail(RT_E_INVALID, "null argument");
+  return features_read(f, f->feat, f->feat_samples, "rt_denoise_features", host_words, n_feat);
+}
+
+int rt_denoise_albedo_read(const rt_film* f, int64_t* host_words, int32_t* n_albedo) {
+  if (!f) return fail(RT_E_INVALID, "null argument");
+  return features_read(f, f->feat2, f->albedo_samples, "rt_denoise_albedo", host_words, n_albedo);
+}
+
+int rt_denoise_film(rt_film* f, const rt_denoise_params* p, void* d_out_rgb, void* hip_stream) {
+  if (!f || !d_out_rgb) return fail(RT_E_INVALID, "null argument");
+  rt_denoise_params dp;
+  rt_dn_defaults(&dp);
+  if (p) dp = *p;
+  std::lock_guard<std::mutex> lock(f->mu);
+  if (int rc = denoise_check(f, &dp)) return rc;
+  if (int rc = film_denoise(f, &dp, d_out_rgb, (hipStream_t)hip_stream)) return rc;
+  f->last = (hipStream_t)hip_stream;
+  return RT_OK;
+}
+
+int rt_denoise_film_read(rt_film* f, const rt_denoise_params* p, void* host_out_rgb) {
+  if (!f || !host_out_rgb) return fail(RT_E_INVALID, "null argument");
+  rt_denoise_params dp;
+  rt_dn_defaults(&dp);
+  if (p) dp = *p;
+  std::lock_guard<std::mutex> lock(f->mu);  // (the tile is the film's scratch)
+  if (int rc = denoise_check(f, &dp)) return rc;
+  if (int rc = film_denoise(f, &dp, f->tile, f->last)) return rc;
+  HIP_TRY(hipMemcpyAsync(host_out_rgb, f->tile, f->n_pixels * 3 * elem_size_of(f->f32), hipMemcpyDeviceToHost, f->last));
+  HIP_TRY(hipStreamSynchronize(f->last));
   return RT_OK;
 }
 

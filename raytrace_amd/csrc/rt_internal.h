@@ -497,6 +497,11 @@ int rt_launch_render(const KernelParams64& p, int grid_blocks, int variant, void
 // accum / nanflag -> out (mean over spp, NaN where flagged)
 int rt_launch_resolve(const KernelParams& p, void* stream);
 int rt_launch_resolve(const KernelParams64& p, void* stream);
+// rt_features.hip / rt_features64_nl.hip: the first-hit feature words of samples [0, n_feat) of every
+// tile pixel added to feat (8 int64 per pixel, zeroed by the caller; rt_features.h).  p as a render's
+// (rt_host_render_params) with lds_nodes = 0 and status set
+int rt_launch_features(const KernelParams& p, int variant, unsigned long long* feat, int n_feat, void* stream);
+int rt_launch_features(const KernelParams64& p, int variant, unsigned long long* feat, int n_feat, void* stream);
 #if defined(RT_PHASE_PROF)
 int rt_prof_read_kernel(const KernelParams*, unsigned long long* out, int n);
 int rt_prof_read_kernel(const KernelParams64*, unsigned long long* out, int n);

@@ -12,6 +12,8 @@ of a, b, c samples give exactly the image of `raytrace` at a + b + c samples per
     state = film.state()            # a numpy uint8 array: np.save it, film.restore it later
 
 `raytrace_until` is that loop as one call.  `noise_from_sums` restates the estimator in numpy.
+`film.denoised()` is the image filtered for a preview and `film.features()` its guide buffers
+(raytrace_amd.denoise).
 """
 from __future__ import annotations
 
@@ -59,6 +61,8 @@ class Film:
         self.handle = h
         info = self.info()
         self.shape = (info["rows"], info["width"], 3)
+        self._feature_samples = 0  # n of the feature words on the device (0: not computed)
+        self._albedo_samples = 0   # ... of the remodulation albedo (0: none)
 
     def info(self) -> dict:
         st = _lib.RtFilmInfo()
@@ -100,6 +104,72 @@ class Film:
         v = ctypes.c_double()
         _lib.check(self._lib.rt_film_noise(self.handle, ctypes.c_void_p(m.data_ptr()), ctypes.byref(v)))
         return m.cpu().numpy().reshape(self.shape[:2])
+
+    def feature_words(self, n: int = 8, stream_ptr: int = 0) -> np.ndarray:
+        """The first-hit feature pass over samples [0, n) of every pixel (rt_denoise_features; run
+        again only when n changes) and its integer words: (rows, width, 8) int64 — albedo RGB, normal
+        xyz and the depth sum in units of 2^-32, and the hit count —, in a binary64 film (rows, width,
+        16): those, then the next 32 bits of each sum (denoise.features_from_words)."""
+        if self._feature_samples != int(n):
+            self._feature_samples = 0
+            _lib.check(self._lib.rt_denoise_features(self.handle, int(n), ctypes.c_void_p(stream_ptr or None)))
+            self._feature_samples = int(n)
+        words = np.zeros(self.shape[:2] + (8 if self.precision == "f32" else 16,), np.int64)
+        got = ctypes.c_int32()
+        _lib.check(self._lib.rt_denoise_features_read(self.handle, words.ctypes.data_as(ctypes.c_void_p), ctypes.byref(got)))
+        assert got.value == self._feature_samples
+        return words
+
+    def features(self, n: int = 8) -> dict:
+        """The guide buffers of the primary rays of samples [0, n): `albedo` (rows, width, 3) — the
+        first hit's texture (1 for dielectric, 0 for pitchBlack, the background on a miss) —,
+        `normal` (rows, width, 3) — the mean unit normal facing the ray (0 in a medium or on a miss) —,
+        `depth` (rows, width) — the mean hit distance over the samples that hit — and `coverage`
+        (rows, width), the fraction that hit.  A function of scene, camera and seed: adding samples
+        to the film does not change them, and they are not part of state()."""
+        from .denoise import features_from_words
+        return features_from_words(self.feature_words(n), n)
+
+    def albedo(self, n: int = 64) -> np.ndarray:
+        """The remodulation albedo (rt_denoise_albedo): the first-hit albedo over samples [0, n),
+        (rows, width, 3).  The filter divides the colour by features()'s albedo — the film's own first
+        samples, whose coverage noise at an emitter's or a texture's edge cancels in the quotient — and
+        multiplies the result by this better estimate.  Computed once: it does not change as samples
+        are added."""
+        from .denoise import features_from_words
+        if self._albedo_samples != int(n):
+            self._albedo_samples = 0
+            _lib.check(self._lib.rt_denoise_albedo(self.handle, int(n), None))
+            self._albedo_samples = int(n)
+        words = np.zeros(self.shape[:2] + (8 if self.precision == "f32" else 16,), np.int64)
+        got = ctypes.c_int32()
+        _lib.check(self._lib.rt_denoise_albedo_read(self.handle, words.ctypes.data_as(ctypes.c_void_p), ctypes.byref(got)))
+        assert got.value == self._albedo_samples
+        return features_from_words(words, n)["albedo"]
+
+    def denoised(self, out: np.ndarray | None = None, levels: int = 5, feature_samples: int = 8, albedo_samples: int = 64,
+                 **params) -> np.ndarray:
+        """The image filtered by the variance-guided denoiser (raytrace_amd.denoise; rt_denoise_film):
+        (rows, width, 3) in the film's dtype.  Needs two passes (the variance estimate) and a film of
+        n_shards = 1 (RtUnsupported otherwise: a shard's rows are interleaved with the others').
+        Computes the features (feature_samples: at most the film's samples, so that colour and albedo
+        share their first samples) and the remodulation albedo (albedo_samples; see albedo()) if they
+        are missing.  params: k, sigma_z, sigma_l, sigma_a, eps_n, eps_z, eps_l
+        (denoise.DEFAULT_PARAMS)."""
+        from .denoise import params_struct
+        from .ray import _out_buffer
+        p = params_struct(params, levels=levels)
+        if self._feature_samples != int(feature_samples):
+            self._feature_samples = 0
+            _lib.check(self._lib.rt_denoise_features(self.handle, int(feature_samples), None))
+            self._feature_samples = int(feature_samples)
+        if self._albedo_samples != int(albedo_samples):
+            self._albedo_samples = 0
+            _lib.check(self._lib.rt_denoise_albedo(self.handle, int(albedo_samples), None))
+            self._albedo_samples = int(albedo_samples)
+        out = _out_buffer(out, self.shape, self.dtype)
+        _lib.check(self._lib.rt_denoise_film_read(self.handle, ctypes.byref(p), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
 
     def state(self) -> np.ndarray:
         """The film's state as bytes (header, sums, flags, estimator words): see `unpack_state`."""
@@ -191,12 +261,14 @@ def noise_from_sums(pass_sums, pass_sizes) -> dict:
 
 
 def raytrace_until(settings: CameraSettings, world, seed, noise: float, batch: int = 16, max_spp: int | None = None,
-                   **kw):
+                   denoise: bool = False, denoise_params: dict | None = None, **kw):
     """Render in passes of `batch` samples until the frame's noise figure (Film.noise) is at most
     `noise` (checked from the second pass on) or `max_spp` samples per pixel are reached (default
     cs_samplesPerPixel; the last pass is cut to fit).  Returns (image, info): the image is
     `raytrace`'s at info["spp"] samples; info has spp, passes, noise (None before two passes) and
-    converged.  kw: Film's precision, device, n_shards, shard, row_block."""
+    converged.  denoise=True returns the denoised image instead (Film.denoised with denoise_params;
+    it needs two passes: max_spp > batch) and keeps the raw one in info["raw"].  kw: Film's
+    precision, device, n_shards, shard, row_block."""
     if batch <= 0:
         from .errors import RtInvalid
         raise RtInvalid("batch must be positive")
@@ -212,4 +284,8 @@ def raytrace_until(settings: CameraSettings, world, seed, noise: float, batch: i
                 if figure <= noise:
                     converged = True
                     break
-        return film.image(), dict(spp=spp, passes=passes, noise=figure, converged=converged)
+        info = dict(spp=spp, passes=passes, noise=figure, converged=converged)
+        if denoise:
+            info["raw"] = film.image()
+            return film.denoised(**(denoise_params or {})), info
+        return film.image(), info
