@@ -715,6 +715,22 @@ RT_FN bool box_face(const RT_CAS DevBox* B, int f, real q, const RayCtx& R, int&
   if (with_prim) prim = box_field(B->prim_base, B->prim_code, f, present);
   return present && !is_self<kInst>(R, gid, -1) && q >= RL(0.0);
 }
+// 1 / (a_k . d) for the slab test, kept finite for a_k . d = +-0 (an axis parallel to the ray): with
+// an infinite one t1 = fma(-s, inf, inf) is NaN for a ray inside that axis's slab, whose exit then
+// looked like -inf, and the ray missed the box (tests/test_shading_probe.py
+// test_box_group_axis_parallel_rays).  With a finite M the slab is (-s M, (1 - s) M): open to the
+// other two axes' hits when 0 < s < 1 and empty otherwise, as in exact arithmetic; if s M
+// overflows, both ends are infinities of one sign, an empty slab as well.  Binary64: a clamp to
+// +-1e300 (two instructions in the guarded branch; the compare-and-select forms spilled VGPRs in
+// the flat binary64 kernels); FP32: safe_rcp (+-1e20).  A NaN comes out finite in both, as in
+// prep_ray: such a ray's radiance is not finite whatever it hits.
+RT_FN real box_rcp(real d) {
+#if RT_F64
+  return RMAX(-RL(1e300), RMIN(RL(1e300), RT_RCP(d)));
+#else
+  return safe_rcp(d);
+#endif
+}
 template <bool kKeyOnly, bool kInst = false>
 RT_FN void test_box(const RT_CAS DevBox* B, const RayCtx& R, real tmin_up, Closest& C) {
   RT_COUNT(1);
@@ -726,7 +742,8 @@ RT_FN void test_box(const RT_CAS DevBox* B, const RayCtx& R, real tmin_up, Close
   // Binary64: the three slab reciprocals from ONE reciprocal of their product, 1 / d_k =
   // (d_i d_j) / (d_0 d_1 d_2) — one v_rcp_f64 and its correction instead of three (within ~4 ulp
   // of 1 / d_k).  A product that is zero, denormal or infinite (an axis parallel to the ray)
-  // takes the three guarded reciprocals instead, a branch no lane normally enters.
+  // takes the three guarded reciprocals instead, a branch no lane normally enters.  Guarded:
+  // box_rcp, finite for a_k . d = +-0 (see there).
   real dk[3], invk[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) dk[k] = dot(ax[k], R.d);
@@ -738,7 +755,7 @@ RT_FN void test_box(const RT_CAS DevBox* B, const RayCtx& R, real tmin_up, Close
     invk[2] = r * d01;
     if (!(RABS(p) >= RL(1e-300) && RABS(p) <= RL(1e300))) {
 #pragma unroll
-      for (int k = 0; k < 3; ++k) invk[k] = RT_RCP(dk[k]);
+      for (int k = 0; k < 3; ++k) invk[k] = box_rcp(dk[k]);
     }
   }
 #endif
@@ -747,7 +764,7 @@ RT_FN void test_box(const RT_CAS DevBox* B, const RayCtx& R, real tmin_up, Close
 #if RT_F64 && !defined(RT_BOX_THREE_RCP)
     const real inv = invk[k];
 #else
-    const real inv = RT_RCP(dot(ax[k], R.d));
+    const real inv = box_rcp(dot(ax[k], R.d));
 #endif
     // s_k = a_k . (o - c) as a_k . o - a_k . c (DevBox::sc, host binary64): one FMA chain
     const real s = RFMA(ax[k].x, R.o.x, RFMA(ax[k].y, R.o.y, RFMA(ax[k].z, R.o.z, -B->sc[k])));
@@ -855,7 +872,8 @@ RT_FN HitInfo surface_info(const KernelParams& P, cfp prims, int pi, const RayCt
       on = mk3(dot(ldc3(fr), outward), dot(ldc3(fr + 4), outward), dot(ldc3(fr + 8), outward));
     }
     // sphereUV (Geometry.hs:100-104)
-    h.u = RATAN2(on.x, on.z) * (RL(0.5) / kPi) + RL(0.5);
+    // (max: at the seam atan2 = -pi and a fused -pi (0.5 / pi) + 0.5 is -1e-17, not 0; u <= 1 holds as it is)
+    h.u = RMAX(RL(0.0), RATAN2(on.x, on.z) * (RL(0.5) / kPi) + RL(0.5));
     h.v = RACOS(RMIN(RL(1.0), RMAX(-RL(1.0), -on.y))) * (RL(1.0) / kPi);
   } else {
     f3 n = xyz(a);
@@ -879,6 +897,13 @@ RT_FN HitInfo surface_info(const KernelParams& P, cfp prims, int pi, const RayCt
 // Perlin noise (Noise.hs:21-45): gradients at the 8 lattice corners, smoothstep weights.
 // Kept compact (corner loop not unrolled) so the rarely used noise textures do not raise the
 // register allocation of the whole lane loop.
+// Domain: the lattice index is (int)floor(x), so every layer's coordinate must stay inside the int
+// range, |freq p + shift| 2^(layers - 1) < 2^31 (the reference floors to a 64-bit Int and keeps the low
+// 8 bits, Noise.hs:23-36; beyond 2^31 the device saturates and the host emulator gives INT_MIN, both
+// a wrong cell).  Inside it the cells are the reference's, negative ones included
+// (tests/test_shading_probe.py test_perlin_and_fractal_noise asserts |q| 2^(layers - 1) < 2^30).
+// A reduction modulo 256 before the conversion would lift the limit at a few more instructions
+// per layer in kernels that sit at their register budget; no scene comes near 2^31 / 64.
 RT_FN real smooth3(real x) { return x * x * (RL(3.0) - RL(2.0) * x); }
 RT_FN real perlin_noise(const RT_CAS int* perm, cfp grad, f3 p) {
   const real x0 = RFLOOR(p.x), y0 = RFLOOR(p.y), z0 = RFLOOR(p.z);
@@ -1486,6 +1511,43 @@ RT_FN void medium_event(const KernelParams& P, int m, uint32_t pix, int sample, 
 // the target loop is left to it: Tf = f pdf1, *apdf = remProb pdf1, and the lane loop divides the
 // throughput by the whole pdf once that test has added the target's term.  Same draws, same
 // branches; the throughput factor's roundings come in another order.
+// h.n + unit_vector(a, b) for the hemisphere sampler, and the vector itself.  On the device the
+// sampler's products r cos, r sin are fused into the sum explicitly: the compiler does so by itself
+// where the vector is used only in the sum (the diffuse forms, the deferred flat loop) but not where
+// it is also used alone (the full-material form), and the two compiled forms of shade_event gave
+// different lambertian directions (tests/test_shading_probe.py
+// test_lambertian_forms_agree_bit_for_bit).  The emulator is built without contraction throughout.
+// normalize with |v|^2 as one fixed chain of fused operations on the device (the compiler's own choice
+// of which product of x x + y y + z z stays unfused differs between instantiations)
+RT_FN f3 normalize_fused(f3 v) {
+#ifdef RT_HOST_EMU
+  return normalize(v);
+#else
+  const real l = RFMA(v.z, v.z, RFMA(v.y, v.y, v.x * v.x));
+#if RT_F64
+  if (RABS(l) <= RL(1e-12) || RABS(RL(1.0) - l) <= RL(1e-12)) return v;
+#else
+  if (l <= RL(1e-12)) return v;
+#endif
+  return RT_RSQRT(l) * v;
+#endif
+}
+template <bool kFlatLoop = false>
+RT_FN f3 normal_plus_unit_vector(f3 n, uint32_t a, uint32_t b, f3& uu) {
+  real z = RL(1.0) - RL(2.0) * u01(a);
+  real r = RT_SQRT(RMAX(RL(0.0), RL(1.0) - z * z));
+  real s, c;
+  if constexpr (kFlatLoop)
+    RT_SINCOS_TURNS_S(u01(b), &s, &c);
+  else
+    RT_SINCOS_TURNS(u01(b), &s, &c);
+  uu = mk3(r * c, r * s, z);
+#ifdef RT_HOST_EMU
+  return n + uu;
+#else
+  return mk3(RFMA(r, c, n.x), RFMA(r, s, n.y), n.z + z);
+#endif
+}
 template <bool kMats, bool kEarly, class... Defer>
 RT_FN bool mixture_scatter(const KernelParams& P, const HitInfo& h, const RayCtx& R, const u4& w, const DevMaterial& Mt,
                            bool hemi, f3 tex, f3& newdir, f3& Tf, Defer... apdf) {
@@ -1504,20 +1566,22 @@ RT_FN bool mixture_scatter(const KernelParams& P, const HitInfo& h, const RayCtx
   // profiles/target_defer): the diffuse flat classes, whose scatter is always hemispherical
   if constexpr (kDefer) {
     if (choice < 0) {
-      dir = h.n + unit_vector<true>(w.y, w.z);
+      f3 uu;
+      dir = normal_plus_unit_vector<true>(h.n, w.y, w.z, uu);
     } else {
       const DevTarget& Tg = P.targets[choice];
       f3 lp = ld3(Tg.q) + u01(w.y) * ld3(Tg.u) + u01(w.z) * ld3(Tg.v);
       dir = lp - h.p;
     }
-    dir = normalize(dir);
+    dir = normalize_fused(dir);
   } else if (choice < 0) {
-    f3 uu = unit_vector(w.y, w.z);
-    dir = hemi ? normalize(h.n + uu) : uu;
+    f3 uu;
+    const f3 nu = normal_plus_unit_vector(h.n, w.y, w.z, uu);
+    dir = hemi ? normalize_fused(nu) : uu;
   } else {
     const DevTarget& Tg = P.targets[choice];
     f3 lp = ld3(Tg.q) + u01(w.y) * ld3(Tg.u) + u01(w.z) * ld3(Tg.v);
-    dir = normalize(lp - h.p);
+    dir = normalize_fused(lp - h.p);  // (as the deferred loop's one normalisation after the join)
   }
   real pdf1 = hemi ? dot(dir, h.n) * (RL(1.0) / kPi) : RL(0.25) / kPi;
   if constexpr (kEarly)

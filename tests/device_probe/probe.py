@@ -18,7 +18,12 @@ LIB = os.path.join(HERE, "_build", "librt_probe.so")
 _lib = None
 
 # argument kinds: ("int" | "u32") scalars, ("in", dtype, per-element width), ("out", dtype, width);
-# dtype "real" is the precision's float type
+# dtype "real" is the precision's float type.  ("rec", name): one Dev* record per element as raw bytes,
+# per-element width sizeof(record) in the chosen precision (tests/kernel_emu/emu.py record_dtypes(precision)
+# [name]; a structured array of that dtype or its bytes).  ("table", dtype): an array of any length shared
+# by all elements (dtype "bytes": records' raw bytes).  ("kp",): the call's KernelParams by value, from a
+# dict: mats (DevMaterial records, one per element), med_mat, key0, key1, targets (DevTarget records),
+# cfg (rem_prob, bg_kind, bg0, bg1) -- built on the host by probe_body.h pb_shade_params
 SIGS = {
     "math1": [("int",), ("in", "real", 1), ("out", "real", 1)],
     "uniform": [("int",), ("in", np.uint32, 1), ("out", "real", 1)],
@@ -30,6 +35,19 @@ SIGS = {
               ("in", np.int32, 1), ("out", "real", 1), ("out", "real", 1), ("out", np.int32, 1)],
     "target": [("in", "real", 12), ("in", "real", 3), ("in", "real", 3), ("out", np.int32, 1), ("out", "real", 1),
                ("out", "real", 1)],
+    "texture": [("rec", "texs"), ("table", "real"), ("table", np.int32), ("table", "real"), ("in", "real", 2),
+                ("in", "real", 3), ("out", "real", 3)],
+    "noise": [("int",), ("table", np.int32), ("table", "real"), ("in", "real", 3), ("out", "real", 1)],
+    "surface": [("int",), ("in", "real", 16), ("in", "real", 6), ("table", "real"), ("in", "real", 3), ("in", "real", 3),
+                ("in", "real", 1), ("out", "real", 3), ("out", "real", 3), ("out", np.int32, 1), ("out", "real", 2),
+                ("out", np.int32, 1)],
+    "box": [("int",), ("table", "bytes"), ("in", "real", 3), ("in", "real", 3), ("in", "real", 1), ("in", np.int32, 1),
+            ("out", "real", 1), ("out", np.int32, 1), ("out", np.int32, 1)],
+    "medium": [("in", np.int32, 1), ("in", np.uint32, 4), ("in", "real", 1), ("in", "real", 2), ("in", "real", 1),
+               ("out", "real", 1), ("out", np.int32, 1)],
+    "shade": [("int",), ("kp",), ("in", "real", 16), ("in", np.int32, 1), ("in", "real", 7), ("in", np.uint32, 3),
+              ("in", "real", 6), ("out", np.int32, 1), ("out", "real", 3), ("out", "real", 3), ("out", "real", 3),
+              ("out", "real", 3), ("out", np.int32, 1)],
     "node": [("in", "real", 3), ("in", "real", 3), ("in", np.float32, 6), ("in", "real", 2), ("out", np.int32, 1)],
 }
 
@@ -54,11 +72,43 @@ def _emu_lib():
     return emu.lib()
 
 
+def record_size(precision, name):
+    _emu_lib()
+    import emu
+    return emu.record_dtypes(precision)[name].itemsize
+
+
 def sincos_table():
     """The (sin, cos) table of rt_sincos_table.h as the compiler reads it: (128, 2) float64."""
     out = np.zeros(4096, np.float64)
     n = _emu_lib().rt_emu_probe_sincos_table(out.ctypes.data_as(ctypes.c_void_p))
     return out[:2 * n].reshape(n, 2)
+
+
+def _kernel_params(precision, kp, mats_address):
+    """The KernelParams of a shade probe call as a ctypes structure to pass by value (its bytes come
+    from the host builder in the emulator library; `mats_address`: where the call's material records
+    are, host or device)."""
+    f = getattr(_emu_lib(), f"rt_emu_probe_shade_params_{precision}")
+    f.restype = ctypes.c_longlong
+    targets = np.ascontiguousarray(kp.get("targets", np.zeros(0, np.uint8))).reshape(-1).view(np.uint8).copy()
+    n_targets = targets.size // record_size(precision, "targets")
+    assert targets.size == n_targets * record_size(precision, "targets")
+    cfg = np.ascontiguousarray(kp["cfg"], np.float64)
+    assert cfg.size == 8
+    tg = np.concatenate([targets, np.zeros(16, np.uint8)])
+    def build(out, cap):
+        return f(out, ctypes.c_longlong(cap), ctypes.c_void_p(mats_address), ctypes.c_int(int(kp.get("med_mat", 0))),
+                 ctypes.c_uint32(int(kp["key0"])), ctypes.c_uint32(int(kp["key1"])), ctypes.c_int(n_targets),
+                 tg.ctypes.data_as(ctypes.c_void_p), cfg.ctypes.data_as(ctypes.c_void_p))
+    size = build(None, 0)
+    assert size > 0 and size % 8 == 0, size
+
+    class KernelParams(ctypes.Structure):
+        _fields_ = [("words", ctypes.c_uint64 * (size // 8))]
+    P = KernelParams()
+    assert build(ctypes.byref(P), size) == size
+    return P
 
 
 def call(backend, precision, name, *inputs):
@@ -71,6 +121,25 @@ def call(backend, precision, name, *inputs):
         if a[0] in ("int", "u32"):
             v = inputs.pop(0)
             plan.append(("scalar", ctypes.c_int(int(v)) if a[0] == "int" else ctypes.c_uint32(int(v))))
+            continue
+        if a[0] == "kp":
+            plan.append(("kp", inputs.pop(0)))
+            continue
+        if a[0] in ("rec", "table"):
+            x = np.ascontiguousarray(inputs.pop(0))
+            if a[0] == "rec" or a[1] == "bytes":
+                x = x.reshape(-1).view(np.uint8).copy()
+            else:
+                x = np.require(x, real if a[1] == "real" else a[1], ["C", "W"]).reshape(-1)
+            if a[0] == "rec":
+                w = record_size(precision, a[1])
+                assert x.size % w == 0, (name, x.size, w)
+                if n is None:
+                    n = x.size // w
+                assert x.size == n * w, (name, x.size, n, w)
+            if x.size == 0:  # an empty table: never read, but a valid address
+                x = np.zeros(16, x.dtype)
+            plan.append(("in", x))
             continue
         dt = real if a[1] == "real" else a[1]
         if a[0] == "in":
@@ -89,6 +158,10 @@ def call(backend, precision, name, *inputs):
         for p in plan:
             if p[0] == "scalar":
                 args.append(p[1])
+            elif p[0] == "kp":
+                mats = np.ascontiguousarray(p[1]["mats"]).reshape(-1).view(np.uint8).copy()
+                keep.append(mats)
+                args.append(_kernel_params(precision, p[1], mats.ctypes.data))
             elif p[0] == "in":
                 keep.append(p[1])
                 args.append(p[1].ctypes.data_as(ctypes.c_void_p))
@@ -108,6 +181,10 @@ def call(backend, precision, name, *inputs):
     for p in plan:
         if p[0] == "scalar":
             args.append(p[1])
+        elif p[0] == "kp":
+            t = torch.from_numpy(np.ascontiguousarray(p[1]["mats"]).reshape(-1).view(np.uint8).copy()).cuda()
+            keep.append(t)
+            args.append(_kernel_params(precision, p[1], t.data_ptr()))
         elif p[0] == "in":
             x = p[1]
             t = torch.from_numpy(x.view(as_signed.get(x.dtype, x.dtype))).cuda()

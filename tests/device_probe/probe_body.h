@@ -121,6 +121,136 @@ RT_FN void pb_node(int i, const real* o, const real* d, const float* box, const 
 }
 #endif
 
+// ---- the shading half.  Records the kernel reads through constant-address-space pointers come in
+// as arrays of the record's bytes (the host builder's, tests/kernel_emu rt_emu_scene_arrays), and
+// the KernelParams member the function reads is pointed at them; only those members are filled.
+// eval_texture<true>: element i reads texture record i of `texs` at (u, v) = uv[2 i ..], p = p[3 i ..];
+// texels / perm / grad: the tables of the whole call
+RT_FN void pb_texture(int i, const unsigned char* texs, const real* texels, const int* perm, const real* grad,
+                      const real* uv, const real* p, real* rgb) {
+  RT_NS::KernelParams P{};
+  P.texs = (const RT_NS::DevTexture*)texs;
+  P.texels = texels;
+  P.perlin_perm = perm;
+  P.perlin_grad = grad;
+  const f3 c = eval_texture<true>(P, i, uv[2 * i], uv[2 * i + 1], ld3(p + 3 * i));
+  rgb[3 * i] = c.x, rgb[3 * i + 1] = c.y, rgb[3 * i + 2] = c.z;
+}
+// op 0 perlin_noise(q), otherwise fractal_noise(depth = op, q)
+RT_FN void pb_noise(int i, int op, const int* perm, const real* grad, const real* q, real* y) {
+  const f3 p = ld3(q + 3 * i);
+  y[i] = op == 0 ? perlin_noise((const RT_CAS int*)perm, cf(grad), p)
+                 : fractal_noise((const RT_CAS int*)perm, cf(grad), op, p);
+}
+// surface_info of primitive record i (16 reals) with prim_uv row i (6 reals) for the ray (o, d) at t;
+// out: p, n (3 reals each), front, (u, v), gid
+RT_FN void pb_surface(int i, int need_uv, const real* prims, const real* prim_uv, const real* uvframes, const real* o,
+                      const real* d, const real* t, real* hp, real* hn, int* front, real* uv, int* gid) {
+  RT_NS::KernelParams P{};
+  P.prims = prims;
+  P.prim_uv = prim_uv;
+  P.uvframes = uvframes;
+  RayCtx R{};
+  R.o = ld3(o + 3 * i);
+  R.d = ld3(d + 3 * i);
+  const HitInfo h = surface_info(P, cf(prims), i, R, t[i], need_uv != 0);
+  hp[3 * i] = h.p.x, hp[3 * i + 1] = h.p.y, hp[3 * i + 2] = h.p.z;
+  hn[3 * i] = h.n.x, hn[3 * i + 1] = h.n.y, hn[3 * i + 2] = h.n.z;
+  front[i] = h.front ? 1 : 0;
+  uv[2 * i] = h.u, uv[2 * i + 1] = h.v;
+  gid[i] = h.gid;
+}
+// test_box<false> of box record `box` (one per call: the record is wave-uniform in the kernel) for a
+// ray without a hit so far; out: Closest's t (+inf: no hit), primitive and key order (-1: no hit)
+RT_FN void pb_box(int i, int box, const unsigned char* boxes, const real* o, const real* d, const real* tmin,
+                  const int* self_gid, real* t, int* prim, int* ord) {
+  RayCtx R{};
+  R.o = ld3(o + 3 * i);
+  R.d = ld3(d + 3 * i);
+  R.self_gid = self_gid[i];
+  R.self_inst = -1;
+  Closest C = no_hit();
+  test_box<false>((const RT_CAS RT_NS::DevBox*)boxes + box, R, float_up(tmin[i]), C);
+  t[i] = C.t;
+  prim[i] = C.prim;
+#if RT_F64
+  ord[i] = C.prim < 0 ? -1 : C.ord;
+#else
+  ord[i] = C.prim < 0 ? -1 : (int)(unsigned)(C.key & 0xffffffffull);
+#endif
+}
+// medium_draw of medium m[i] (0 .. 3: the word selector) with neg_inv_density nid[i], the Philox block
+// w[4 i ..], the segment (lo, hi) = lohi[2 i ..] and the closest hit so far tb[i]
+RT_FN void pb_medium(int i, const int* m, const uint32_t* w, const real* nid, const real* lohi, const real* tb,
+                     real* tbest, int* hit_medium) {
+  RT_NS::KernelParams P{};
+  const int mm = m[i] & 3;
+  P.media[mm].neg_inv_density = nid[i];
+  real t = tb[i];
+  int hm = -1;
+  medium_draw(P, mm, u4{w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]}, lohi[2 * i], lohi[2 * i + 1], t, hm);
+  tbest[i] = t;
+  hit_medium[i] = hm;
+}
+// shade_event<2, true, false> (form 1) or <0, false, false> (form 0) of element i.  KP: the call's
+// KernelParams BY VALUE, as the render kernels take theirs (philox pins the key to scalar registers, so
+// the struct must be a kernel argument, not a per-thread copy); pb_shade_params below fills it on the
+// host.  how[i]: 0 a hit on primitive record i (prims, 16 reals) with material record i of KP.prim_shade,
+// 1 a medium hit (medium 0, material KP.media[0].material of KP.mats), 2 a miss.  ray: o, d, t (7 reals);
+// ctr: pix, sample, seg; LT: L, T (6 reals).  out: terminate, L, np, nd, Tf, ngid (np, nd, Tf, ngid as
+// shade() presets them: NaN / RT_EMPTY_ROOT on the emulator; the incoming ray, 1, self_gid = -1 on the device)
+RT_FN void pb_shade(int i, int form, const RT_NS::KernelParams& P, const real* prims, const int* how, const real* ray,
+                    const uint32_t* ctr, const real* LT, int* term, real* Lo, real* np, real* nd, real* Tf, int* ngid) {
+  RayCtx R{};
+  R.o = ld3(ray + 7 * i);
+  R.d = ld3(ray + 7 * i + 3);
+  R.self_gid = -1;
+  R.self_inst = -1;
+  const real tb = ray[7 * i + 6];
+  f3 L = ld3(LT + 6 * i);
+  const f3 T = ld3(LT + 6 * i + 3);
+#ifdef RT_HOST_EMU
+  f3 p2 = mk3(RT_NAN, RT_NAN, RT_NAN), d2 = p2, tf = p2;
+  int g2 = RT_EMPTY_ROOT;
+#else
+  f3 p2 = R.o, d2 = R.d, tf = mk3(RL(1.), RL(1.), RL(1.));
+  int g2 = R.self_gid;
+#endif
+  const int best = how[i] == 0 ? i : -1, hm = how[i] == 1 ? 0 : -1;
+  const uint32_t pix = ctr[3 * i];
+  const int sample = (int)ctr[3 * i + 1], seg = (int)ctr[3 * i + 2];
+  const bool e = form ? shade_event<2, true, false>(P, cf(prims), pix, sample, seg, tb, best, hm, R, L, T, -1, p2, d2, tf, g2)
+                      : shade_event<0, false, false>(P, cf(prims), pix, sample, seg, tb, best, hm, R, L, T, -1, p2, d2, tf, g2);
+  term[i] = e ? 1 : 0;
+  Lo[3 * i] = L.x, Lo[3 * i + 1] = L.y, Lo[3 * i + 2] = L.z;
+  np[3 * i] = p2.x, np[3 * i + 1] = p2.y, np[3 * i + 2] = p2.z;
+  nd[3 * i] = d2.x, nd[3 * i + 1] = d2.y, nd[3 * i + 2] = d2.z;
+  Tf[3 * i] = tf.x, Tf[3 * i + 1] = tf.y, Tf[3 * i + 2] = tf.z;
+  ngid[i] = g2;
+}
+#ifdef RT_HOST_EMU
+// The KernelParams of a pb_shade call (host side, both backends): only the members shade_event reads.
+// mats: the address (host or device) of the call's DevMaterial records (prim_shade and mats); targets:
+// n_targets DevTarget records on the host; cfg: rem_prob, bg_kind, bg0, bg1 (8 doubles).  Returns
+// sizeof(KernelParams); the struct is written when cap allows.
+static long long pb_shade_params(void* out, long long cap, const void* mats, int med_mat, uint32_t k0, uint32_t k1,
+                                 int n_targets, const void* targets, const double* cfg) {
+  RT_NS::KernelParams P{};
+  if (n_targets < 0 || n_targets > RT_MAX_TARGETS) return -1;
+  P.prim_shade = (const RT_NS::DevMaterial*)mats;
+  P.mats = (const RT_NS::DevMaterial*)mats;
+  P.media[0].material = med_mat;
+  P.key0 = k0, P.key1 = k1;
+  P.n_targets = n_targets;
+  for (int k = 0; k < n_targets; ++k) P.targets[k] = ((const RT_NS::DevTarget*)targets)[k];
+  P.rem_prob = (real)cfg[0];
+  P.cam.bg_kind = (int)cfg[1];
+  for (int k = 0; k < 3; ++k) P.cam.bg0[k] = (real)cfg[2 + k], P.cam.bg1[k] = (real)cfg[5 + k];
+  if (out && cap >= (long long)sizeof P) std::memcpy(out, &P, sizeof P);
+  return (long long)sizeof P;
+}
+#endif
+
 #define RT_PROBE_UNPACK(...) __VA_ARGS__
 RT_PROBE_DEFINE(math1, (int op, const real* x, real* y), (op, x, y))
 RT_PROBE_DEFINE(uniform, (int op, const uint32_t* w, real* y), (op, w, y))
@@ -134,6 +264,27 @@ RT_PROBE_DEFINE(isect,
                 (kind, rec, o, d, tmin, self, t, q, take))
 RT_PROBE_DEFINE(target, (const real* tg, const real* o, const real* d, int* hit, real* t, real* rinv),
                 (tg, o, d, hit, t, rinv))
+RT_PROBE_DEFINE(texture,
+                (const unsigned char* texs, const real* texels, const int* perm, const real* grad, const real* uv,
+                 const real* p, real* rgb),
+                (texs, texels, perm, grad, uv, p, rgb))
+RT_PROBE_DEFINE(noise, (int op, const int* perm, const real* grad, const real* q, real* y), (op, perm, grad, q, y))
+RT_PROBE_DEFINE(surface,
+                (int need_uv, const real* prims, const real* prim_uv, const real* uvframes, const real* o, const real* d,
+                 const real* t, real* hp, real* hn, int* front, real* uv, int* gid),
+                (need_uv, prims, prim_uv, uvframes, o, d, t, hp, hn, front, uv, gid))
+RT_PROBE_DEFINE(box,
+                (int box, const unsigned char* boxes, const real* o, const real* d, const real* tmin, const int* self_gid,
+                 real* t, int* prim, int* ord),
+                (box, boxes, o, d, tmin, self_gid, t, prim, ord))
+RT_PROBE_DEFINE(medium,
+                (const int* m, const uint32_t* w, const real* nid, const real* lohi, const real* tb, real* tbest,
+                 int* hit_medium),
+                (m, w, nid, lohi, tb, tbest, hit_medium))
+RT_PROBE_DEFINE(shade,
+                (int form, RT_NS::KernelParams KP, const real* prims, const int* how, const real* ray,
+                 const uint32_t* ctr, const real* LT, int* term, real* Lo, real* np, real* nd, real* Tf, int* ngid),
+                (form, KP, prims, how, ray, ctr, LT, term, Lo, np, nd, Tf, ngid))
 #if RT_NODE_F32
 RT_PROBE_DEFINE(node, (const real* o, const real* d, const float* box, const real* tr, int* accept),
                 (o, d, box, tr, accept))

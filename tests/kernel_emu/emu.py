@@ -96,6 +96,66 @@ DIGEST_ITEMS = (["nodes", "perlin_perm", "prim_mat", "flat_sets", "scalars"] + [
                 + ["f64." + a for a in _ARRAYS])
 
 
+def record_dtypes(precision):
+    """numpy layouts (C alignment, padding included) of the Dev* records of rt_internal.h in one
+    precision, and of the plain arrays scene_arrays returns."""
+    R = "<f8" if precision == "f64" else "<f4"
+    i = "<i4"
+    return {
+        "mats": np.dtype([("kind", i), ("tex", i), ("param", R), ("tex_const", i), ("c0", R, (3,)), ("pad", R)], align=True),
+        "texs": np.dtype([("kind", i), ("nu", i), ("nv", i), ("off", i), ("c0", R, (3,)), ("c1", R, (3,)),
+                          ("prm", R, (8,)), ("pad", R, (2,))], align=True),
+        "boxes": np.dtype([("sc", R, (3,)), ("ord_base", i), ("a0", R, (3,)), ("ord_code", i), ("a1", R, (3,)),
+                           ("gid_base", i), ("a2", R, (3,)), ("gid_code", i), ("prim_base", i), ("prim_code", i),
+                           ("pad", i, (2,))], align=True),
+        "flat_sets": np.dtype([("first", i), ("end_quad", i), ("end_tri", i), ("end_sphere", i), ("end", i),
+                               ("box_first", i), ("box_end", i), ("pad", i)], align=True),
+        "targets": np.dtype([(k, R, (3,)) for k in ("q", "u", "v", "n", "wa", "wb", "cr")]
+                            + [("prob", R), ("thresh", R), ("prob_icr", R)], align=True),
+    }
+
+
+SCENE_ARRAYS = ["prims", "prim_uv", "prim_shade", "mats", "texs", "texels", "uvframes", "boxes", "perlin_perm",
+                "perlin_grad", "flat_sets", "flat_recs"]
+
+
+def scene_arrays(world, precision="f64"):
+    """{name: array} of the host build of `world` in one precision (rt_emu_scene_arrays, read-only):
+    prims (n, 16), prim_uv (n, 6), flat_recs (n, 16), uvframes (n, 12), texels (n, 4), perlin_grad (256, 4),
+    perlin_perm (int32), and the record arrays prim_shade, mats, texs, boxes, flat_sets as structured
+    arrays of record_dtypes (their bytes as the builder wrote them)."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from raytrace_amd import _lib as R
+    from raytrace_amd.scene import FlatScene, flatten
+    flat = world if isinstance(world, FlatScene) else flatten(world)
+    sc = R.scene_struct(flat)
+    real = np.float64 if precision == "f64" else np.float32
+    dts = record_dtypes(precision)
+    dts["prim_shade"] = dts["mats"]
+    width = {"prims": 16, "prim_uv": 6, "flat_recs": 16, "uvframes": 12, "texels": 4, "perlin_grad": 4}
+    out = {}
+    f = lib().rt_emu_scene_arrays
+    for name in SCENE_ARRAYS:
+        info = (ctypes.c_longlong * 2)()
+        rc = f(ctypes.byref(sc), ctypes.c_int(precision == "f64"), name.encode(), None, ctypes.c_longlong(0), info)
+        if rc != 0:
+            raise RuntimeError(f"rt_emu_scene_arrays failed {rc}: {lib().rt_emu_last_error().decode()}")
+        buf = np.zeros(max(int(info[0]), 1), np.uint8)
+        rc = f(ctypes.byref(sc), ctypes.c_int(precision == "f64"), name.encode(), buf.ctypes.data_as(ctypes.c_void_p),
+               ctypes.c_longlong(buf.size), info)
+        assert rc == 0, (name, rc)
+        buf = buf[:int(info[0])]
+        if name in dts:
+            assert dts[name].itemsize == info[1], (name, dts[name].itemsize, info[1])
+            out[name] = buf.view(dts[name]).copy()
+        elif name == "perlin_perm":
+            out[name] = buf.view(np.int32).copy()
+        else:
+            out[name] = buf.view(real).reshape(-1, width[name]).copy()
+    return out
+
+
 def scene_digest(world):
     """(rc, error text, {item: [length, "fnv-1a hex"]}) of the host build of `world` (a Geometry or a
     FlatScene): every array and scalar of HostScene in both precisions, so that two builders can be

@@ -63,6 +63,18 @@ namespace rt_emu {
 thread_local long long counters[4];
 }
 
+extern "C" {
+// the KernelParams bytes of a shade probe call (probe_body.h pb_shade_params), for both backends
+long long rt_emu_probe_shade_params_f32(void* out, long long cap, const void* mats, int med_mat, uint32_t k0,
+                                        uint32_t k1, int n_targets, const void* targets, const double* cfg) {
+  return probe32::pb_shade_params(out, cap, mats, med_mat, k0, k1, n_targets, targets, cfg);
+}
+long long rt_emu_probe_shade_params_f64(void* out, long long cap, const void* mats, int med_mat, uint32_t k0,
+                                        uint32_t k1, int n_targets, const void* targets, const double* cfg) {
+  return probe64::pb_shade_params(out, cap, mats, med_mat, k0, k1, n_targets, targets, cfg);
+}
+}
+
 namespace {
 thread_local std::string g_err;
 }  // namespace
@@ -306,5 +318,55 @@ int rt_emu_scene_digest(const rt_scene* sc, uint64_t* out, int n) {
   digest_arrays(H.f32, H.n_media, D);
   digest_arrays(H.f64, H.n_media, D);
   return D.n == 31 ? RT_OK : RT_E_GENERIC;
+}
+}
+
+// Read-only export of the host build's arrays by name (test tooling: the element-wise probes of
+// tests/device_probe are fed the records the product's own builder makes).  The names are those of
+// the digest above; a record array comes as the records' bytes, padding included.
+namespace {
+struct ArrayOut {
+  const char* want;
+  void* out;
+  long long cap;
+  long long* info;  // bytes, bytes per element
+  bool found = false;
+  template <class T>
+  void item(const char* name, const T* p, size_t len) {
+    if (std::strcmp(name, want) != 0) return;
+    found = true;
+    info[0] = (long long)(len * sizeof(T));
+    info[1] = (long long)sizeof(T);
+    if (out && info[0] <= cap && len) std::memcpy(out, p, len * sizeof(T));
+  }
+  template <class T>
+  void item(const char* name, const std::vector<T>& v) { item(name, v.data(), v.size()); }
+};
+template <class R>
+void export_arrays(const HostArraysT<R>& A, ArrayOut& O) {
+  O.item("prims", A.prims), O.item("prim_uv", A.prim_uv), O.item("flat_recs", A.flat_recs);
+  O.item("uvframes", A.uvframes), O.item("texels", A.texels), O.item("perlin_grad", A.perlin_grad);
+  O.item("prim_shade", A.prim_shade), O.item("mats", A.mats), O.item("texs", A.texs), O.item("boxes", A.boxes);
+}
+}  // namespace
+
+extern "C" {
+// info[0] = the array's bytes, info[1] = bytes per element; the bytes are copied when out is not
+// null and cap >= info[0].  An unknown name is RT_E_INVALID.
+int rt_emu_scene_arrays(const rt_scene* sc, int f64, const char* name, void* out, long long cap, long long* info) {
+  if (!name || !info) return RT_E_INVALID;
+  HostScene H;
+  int rc = rt_host_build_scene(sc, H, g_err);
+  if (rc) return rc;
+  ArrayOut O{name, out, cap, info};
+  O.item("perlin_perm", H.perlin_perm);
+  O.item("flat_sets", H.flat_sets, (size_t)(1 + RT_MAX_MEDIA));
+  if (f64) export_arrays(H.f64, O);
+  else export_arrays(H.f32, O);
+  if (!O.found) {
+    g_err = std::string("rt_emu_scene_arrays: no array named ") + name;
+    return RT_E_INVALID;
+  }
+  return RT_OK;
 }
 }
