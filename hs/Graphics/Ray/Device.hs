@@ -43,6 +43,8 @@ module Graphics.Ray.Device
   , raytraceUntil, renderUntilOnDevice
     -- * ... and a denoised preview of it (rt.h rt_denoise_*)
   , raytraceDenoised, renderDenoisedOnDevice
+    -- * ... both over a device list (rt.h rt_multi_film_*: every GPU renders its rows of each pass, one frame)
+  , raytraceUntilWith, raytraceDenoisedWith, renderUntilOnDevices, renderDenoisedOnDevices
     -- * 8-bit output encoded on the device (writeImage / writeImageSqrt of a render, Ray.hs:248-260)
   , Encoding(..), renderImage8, raytraceToFile
     -- * Geometry (Geometry.hs:5-16)
@@ -574,6 +576,20 @@ foreign import ccall safe "rt_denoise_albedo"
   c_rt_denoise_albedo :: Ptr () -> Int32 -> Ptr () -> IO CInt
 foreign import ccall safe "rt_denoise_film_read"
   c_rt_denoise_film_read :: Ptr () -> Ptr () -> Ptr () -> IO CInt
+-- the scene resident on a device list and the multi-device film on it (rt.h rt_multi_film_*): its
+-- frame is read through the rt_film_* / rt_denoise_* calls above
+foreign import ccall safe "rt_multi_scene_create"
+  c_rt_multi_scene_create :: Ptr RtScene -> Ptr Int32 -> Int32 -> Ptr (Ptr ()) -> IO CInt
+foreign import ccall safe "rt_multi_scene_destroy"
+  c_rt_multi_scene_destroy :: Ptr () -> IO CInt
+foreign import ccall safe "rt_multi_film_create"
+  c_rt_multi_film_create :: Ptr () -> Ptr RtCamera -> Word64 -> Ptr RtExec -> Ptr (Ptr ()) -> IO CInt
+foreign import ccall safe "rt_multi_film_destroy"
+  c_rt_multi_film_destroy :: Ptr () -> IO CInt
+foreign import ccall safe "rt_multi_film_add"
+  c_rt_multi_film_add :: Ptr () -> Int32 -> IO CInt
+foreign import ccall safe "rt_multi_film_frame"
+  c_rt_multi_film_frame :: Ptr () -> Ptr (Ptr ()) -> IO CInt
 
 -- Struct layouts of include/rt.h (x86-64).  tests/test_abi.py checks every `-- LAYOUT` line
 -- against the C compiler's offsetof / sizeof.
@@ -988,7 +1004,8 @@ renderUntilWith readout opts settings world gen target batch =
                     rc1 <- c_rt_film_create scene cam (philoxKey gen) ex pfilm
                     r <- if rc1 /= 0 then libraryError rc1 else do
                       film <- peek pfilm
-                      done <- filmPasses film (R.cs_samplesPerPixel settings) target (max 1 batch)
+                      done <- filmPasses (\n -> c_rt_film_add film n nullPtr) film (R.cs_samplesPerPixel settings) target
+                                         (max 1 batch)
                       out <- case done of
                         Left e -> pure (Left e)
                         Right spp -> fmap (\img -> (img, spp)) <$> readout (doPrecision opts) film h w
@@ -998,17 +1015,78 @@ renderUntilWith readout opts settings world gen target batch =
                     pure r
     _ -> pure (Left NotReifiable)
 
--- | Add passes of @batch@ samples to a film until its noise figure is at most @target@ (from the
--- second pass on) or it holds @maxSpp@ samples; the samples per pixel it then holds.
-filmPasses :: Ptr () -> Int -> Double -> Int -> IO (Either RenderError Int)
-filmPasses film maxSpp target batch = alloca $ \pnoise -> go pnoise 0 (0 :: Int)
+-- | 'renderUntilOnDevice' over a device list (rt.h rt_multi_film_*; 'doDevices', by default every
+-- visible GPU; rows dealt in blocks of 'doRowBlock' as the one-shot render deals them): shard k of
+-- every pass renders on the k-th device and is merged into ONE frame on the first, so image and
+-- sample count are exactly 'renderUntilOnDevice''s, whatever the list.
+renderUntilOnDevices :: DeviceOptions -> R.CameraSettings -> Geometry m Material -> StdGen -> Double -> Int
+                     -> IO (Either RenderError (A.Matrix A.S Color, Int))
+renderUntilOnDevices = renderUntilMulti filmImage
+
+-- | 'renderDenoisedOnDevice' over a device list: the frame of 'renderUntilOnDevices', denoised on the
+-- first device (the feature and albedo passes are first-hit passes and run there alone).
+renderDenoisedOnDevices :: DeviceOptions -> R.CameraSettings -> Geometry m Material -> StdGen -> Double -> Int
+                        -> IO (Either RenderError (A.Matrix A.S Color, Int))
+renderDenoisedOnDevices = renderUntilMulti filmDenoised
+
+-- | The passes of 'renderUntilOnDevices' on a multi-device film, then @readout precision frame
+-- height width@ on its frame handle (rt_multi_film_frame: an ordinary one-shard film to read).
+renderUntilMulti :: (Precision -> Ptr () -> Int -> Int -> IO (Either RenderError (A.Matrix A.S Color)))
+                 -> DeviceOptions -> R.CameraSettings -> Geometry m Material -> StdGen -> Double -> Int
+                 -> IO (Either RenderError (A.Matrix A.S Color, Int))
+renderUntilMulti readout opts settings world gen target batch =
+  case (geoDesc world, reifyBackground (R.cs_background settings)) of
+    (Just desc, Just bg) -> do
+      tagged <- tagShared desc
+      case flatten tagged of
+        Nothing -> pure (Left NotReifiable)
+        Just flat -> do
+          devs <- case doDevices opts of
+            Just ds -> pure ds
+            Nothing -> (\n -> [0 .. max 1 n - 1]) <$> deviceCount
+          withCamera settings bg $ \cam ->
+            withFlatScene flat $ \sc ->
+            withArray (map fromIntegral devs :: [Int32]) $ \pdevs ->
+            withExec opts Nothing [] $ \ex -> do      -- n_devices = 0: the devices are the scene's
+              h <- fromIntegral <$> c_rt_image_height cam
+              let w = R.cs_imageWidth settings
+              if h <= 0 || w <= 0 then pure (Left (LibraryError (-2) "empty image")) else
+                alloca $ \pscene -> alloca $ \pfilm -> alloca $ \pframe -> do
+                  rc0 <- c_rt_multi_scene_create sc pdevs (fromIntegral (length devs)) pscene
+                  if rc0 /= 0 then libraryError rc0 else do
+                    scene <- peek pscene
+                    rc1 <- c_rt_multi_film_create scene cam (philoxKey gen) ex pfilm
+                    r <- if rc1 /= 0 then libraryError rc1 else do
+                      film <- peek pfilm
+                      rc2 <- c_rt_multi_film_frame film pframe
+                      out <- if rc2 /= 0 then libraryError rc2 else do
+                        frame <- peek pframe
+                        done <- filmPasses (c_rt_multi_film_add film) frame (R.cs_samplesPerPixel settings) target
+                                           (max 1 batch)
+                        case done of
+                          Left e -> pure (Left e)
+                          Right spp -> do
+                            rc3 <- c_rt_multi_film_frame film pframe   -- every device's status word
+                            if rc3 /= 0 then libraryError rc3
+                              else fmap (\img -> (img, spp)) <$> readout (doPrecision opts) frame h w
+                      _ <- c_rt_multi_film_destroy film
+                      pure out
+                    _ <- c_rt_multi_scene_destroy scene
+                    pure r
+    _ -> pure (Left NotReifiable)
+
+-- | Add passes of @batch@ samples (@add n@) to a film until its noise figure is at most @target@
+-- (from the second pass on) or it holds @maxSpp@ samples; the samples per pixel it then holds.
+-- @film@ is the handle the noise is read from: the film itself, or a multi-device film's frame.
+filmPasses :: (Int32 -> IO CInt) -> Ptr () -> Int -> Double -> Int -> IO (Either RenderError Int)
+filmPasses add film maxSpp target batch = alloca $ \pnoise -> go pnoise 0 (0 :: Int)
   where
     go :: Ptr CDouble -> Int -> Int -> IO (Either RenderError Int)
     go pnoise spp passes
       | spp >= maxSpp = pure (Right spp)
       | otherwise = do
           let n = min batch (maxSpp - spp)
-          rc <- c_rt_film_add film (fromIntegral n) nullPtr
+          rc <- add (fromIntegral n)
           if rc /= 0 then libraryError rc
             else if passes + 1 < 2 then go pnoise (spp + n) (passes + 1)
             else do
@@ -1063,6 +1141,18 @@ raytraceUntil settings world gen noise batch =
            | otherwise -> error ("Graphics.Ray.Device.raytraceUntil: the film failed: " ++ show e)
 {-# NOINLINE raytraceUntil #-}
 
+-- | 'raytraceUntil' over a device list, as 'raytraceWith' is 'raytrace''s: the passes are rendered
+-- by every device of 'doDevices' (default: every visible GPU) into one frame; the image and the
+-- sample count are 'raytraceUntil''s.
+raytraceUntilWith :: R.ToRandom m => DeviceOptions -> R.CameraSettings -> Geometry m Material -> StdGen -> Double -> Int
+                  -> (A.Matrix A.D Color, Int)
+raytraceUntilWith opts settings world gen noise batch =
+  case unsafePerformIO (renderUntilOnDevices opts settings world gen noise batch) of
+    Right (img, spp) -> (A.delay img, spp)
+    Left e | fallback e -> (R.raytrace settings (toReferenceRandom world) gen, R.cs_samplesPerPixel settings)
+           | otherwise -> error ("Graphics.Ray.Device.raytraceUntilWith: the film failed: " ++ show e)
+{-# NOINLINE raytraceUntilWith #-}
+
 -- | 'raytraceUntil' whose image is denoised for a preview (rt.h rt_denoise_*: the film's mean
 -- divided by the first-hit albedo, filtered under normal, depth and variance-scaled luminance
 -- weights, multiplied back).  cs_samplesPerPixel must exceed @batch@ (two passes).  The fallback
@@ -1075,3 +1165,13 @@ raytraceDenoised settings world gen noise batch =
     Left e | fallback e -> (R.raytrace settings (toReferenceRandom world) gen, R.cs_samplesPerPixel settings)
            | otherwise -> error ("Graphics.Ray.Device.raytraceDenoised: the film failed: " ++ show e)
 {-# NOINLINE raytraceDenoised #-}
+
+-- | 'raytraceDenoised' over a device list (see 'raytraceUntilWith'); the filter runs on the first device.
+raytraceDenoisedWith :: R.ToRandom m => DeviceOptions -> R.CameraSettings -> Geometry m Material -> StdGen -> Double
+                     -> Int -> (A.Matrix A.D Color, Int)
+raytraceDenoisedWith opts settings world gen noise batch =
+  case unsafePerformIO (renderDenoisedOnDevices opts settings world gen noise batch) of
+    Right (img, spp) -> (A.delay img, spp)
+    Left e | fallback e -> (R.raytrace settings (toReferenceRandom world) gen, R.cs_samplesPerPixel settings)
+           | otherwise -> error ("Graphics.Ray.Device.raytraceDenoisedWith: the film failed: " ++ show e)
+{-# NOINLINE raytraceDenoisedWith #-}

@@ -361,6 +361,55 @@ int rt_film_state_bytes(const rt_film* f, int64_t* bytes);
 int rt_film_save(const rt_film* f, void* host_buf, int64_t cap);
 int rt_film_load(rt_film* f, const void* host_buf, int64_t bytes);
 
+/* Multi-device film: progressive passes over a multi-device scene's device list, ONE frame.
+ *
+ * The film holds one accumulation state, on the scene's first device: an ordinary one-shard film of
+ * the whole image (the "frame").  A pass of n samples renders shard k's samples [N, N + n) on
+ * devices[k] (the rt_exec row interleave, every device on its own stream, none waiting for another)
+ * and a merge kernel folds each shard's pass sums straight into the frame's rows — run by devices[k]
+ * writing the first device's memory (peer access, as the one-shot resolve), or, without peer access,
+ * by the first device on a copy of the shard's sums and flags.  The sums are integers keyed by global
+ * pixel and sample index, so after the merges the frame is, bit for bit, the state an rt_film on one
+ * device holds after the same passes: sums, NaN flags and the estimator's word.  A saved state does
+ * not depend on the device count.
+ *
+ * rt_multi_film_create: the devices are the scene's (`m` must outlive the film; a list of one device
+ *   and a list that repeats a device are valid; a shard that holds only padding rows — more devices
+ *   than row blocks — contributes nothing).  ex gives the precision and row_block: n_devices 0,
+ *   n_shards 1 (else RT_E_INVALID), no RT_EXEC_ENCODE8_* bit; cs as for rt_film_create.  Every buffer,
+ *   stream and event is allocated here: rt_multi_film_add allocates nothing.
+ * rt_multi_film_add: enqueue one pass on every device; limits as rt_film_add's.  Asynchronous: no
+ *   host thread and no host synchronisation, the work is ordered by events, behind whatever was
+ *   enqueued through the frame handle before (rt_film_resolve, rt_denoise_* on a stream of the
+ *   caller's: the pass's merges wait for that stream).  If it fails after the first enqueue (a HIP
+ *   error), shards enqueued before the failure are merged all the same and the sample count is not
+ *   advanced: the frame holds a partial pass, and only rt_multi_film_reset or rt_multi_film_load
+ *   gives a defined state again.
+ * rt_multi_film_reset, rt_multi_film_load: as rt_film_reset / rt_film_load, after waiting for the
+ *   passes in flight.  Load accepts exactly the state a one-shard rt_film of this frame saves (the
+ *   same header checks, against n_shards = 1).
+ * rt_multi_film_frame: waits for everything enqueued on every device and hands out the frame, which
+ *   the multi film owns (valid until rt_multi_film_destroy).  RT_E_STACK (frame handed out all the
+ *   same) when the traversal-stack word of any of the scene's devices is set.  On the handle every
+ *   reading call works as on any one-shard film — rt_film_read, resolve, noise, get_info,
+ *   state_bytes, save and every rt_denoise_* call (the feature and albedo passes are first-hit
+ *   passes, cheap next to a render pass: they run on the first device alone) — and follows the
+ *   passes added so far, without another rt_multi_film_frame: the asynchronous ones
+ *   (rt_film_resolve, rt_denoise_features / albedo / film) make their stream wait for the merges
+ *   first.  Only rt_multi_film_frame reports the other devices' RT_E_STACK.  rt_film_add,
+ *   rt_film_load, rt_film_reset and rt_film_destroy on it return RT_E_INVALID.
+ * rt_multi_film_copies: the number of shard passes so far whose sums went to the first device by
+ *   the staging copy (0 where every device has peer access to the first). */
+typedef struct rt_multi_film rt_multi_film;
+int rt_multi_film_create(const rt_multi_scene* m, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex,
+                         rt_multi_film** out);
+int rt_multi_film_destroy(rt_multi_film* f);
+int rt_multi_film_reset(rt_multi_film* f);
+int rt_multi_film_add(rt_multi_film* f, int32_t n_samples);
+int rt_multi_film_load(rt_multi_film* f, const void* host_buf, int64_t bytes);
+int rt_multi_film_frame(rt_multi_film* f, rt_film** frame);
+int rt_multi_film_copies(const rt_multi_film* f, int64_t* n);
+
 /* First-hit feature buffers and a variance-guided denoiser for a film's preview.
  *
  * rt_denoise_features: for samples [0, n_feat) of every tile pixel (1 <= n_feat <= 4096), trace the
@@ -395,7 +444,8 @@ int rt_film_load(rt_film* f, const void* host_buf, int64_t bytes);
  *   stay NaN and are not read by their neighbours.  RT_E_INVALID unless the film holds two passes and
  *   its features have been computed, for levels outside 1..8, k outside 0..16 or a sigma / eps that
  *   is not positive; RT_E_UNSUPPORTED for a film of n_shards > 1 (its rows are interleaved with
- *   other shards', and the filter needs a pixel's neighbours).  The working buffers are allocated on
+ *   other shards', and the filter needs a pixel's neighbours; a device list is denoised through
+ *   rt_multi_film_frame's frame, which is one whole image).  The working buffers are allocated on
  *   the first call and kept.  p == NULL: rt_denoise_default_params.
  * rt_denoise_film_read: the same into a host buffer, synchronous (as rt_film_read). */
 typedef struct rt_denoise_params {

@@ -22,6 +22,8 @@ EXPORTED = ["rt_abi_version", "rt_last_error", "rt_device_count", "rt_image_heig
             "rt_multi_scene_create", "rt_multi_scene_destroy", "rt_multi_render",
             "rt_film_create", "rt_film_destroy", "rt_film_reset", "rt_film_add", "rt_film_resolve", "rt_film_read",
             "rt_film_noise", "rt_film_get_info", "rt_film_state_bytes", "rt_film_save", "rt_film_load",
+            "rt_multi_film_create", "rt_multi_film_destroy", "rt_multi_film_reset", "rt_multi_film_add",
+            "rt_multi_film_load", "rt_multi_film_frame", "rt_multi_film_copies",
             "rt_denoise_default_params", "rt_denoise_features", "rt_denoise_albedo", "rt_denoise_features_read", "rt_denoise_albedo_read", "rt_denoise_film",
             "rt_denoise_film_read"]
 
@@ -135,6 +137,14 @@ def load():
     L.rt_film_state_bytes.argtypes = [P, ctypes.POINTER(ctypes.c_int64)]
     L.rt_film_save.argtypes = [P, P, ctypes.c_int64]
     L.rt_film_load.argtypes = [P, P, ctypes.c_int64]
+    L.rt_multi_film_create.argtypes = [P, ctypes.POINTER(RtCameraSettings), ctypes.c_uint64, ctypes.POINTER(RtExec),
+                                       ctypes.POINTER(ctypes.c_void_p)]
+    L.rt_multi_film_destroy.argtypes = [P]
+    L.rt_multi_film_reset.argtypes = [P]
+    L.rt_multi_film_add.argtypes = [P, ctypes.c_int32]
+    L.rt_multi_film_load.argtypes = [P, P, ctypes.c_int64]
+    L.rt_multi_film_frame.argtypes = [P, ctypes.POINTER(ctypes.c_void_p)]
+    L.rt_multi_film_copies.argtypes = [P, ctypes.POINTER(ctypes.c_int64)]
     L.rt_denoise_default_params.argtypes = [ctypes.POINTER(RtDenoiseParams)]
     L.rt_denoise_features.argtypes = [P, ctypes.c_int32, P]
     L.rt_denoise_albedo.argtypes = [P, ctypes.c_int32, P]

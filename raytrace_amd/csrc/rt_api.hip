@@ -3,7 +3,8 @@
 // kernel launch (rt_kernel.hip / rt_kernel64.hip), multi-device scenes (one process, many GPUs:
 // concurrent uploads, shard renders on per-device streams, a device-side gather by peer copies
 // into the first device's framebuffer and ONE device-to-host copy), the 8-bit output epilogue,
-// the progressive film (its state and entry points; kernels in rt_film.hip), error reporting.
+// the progressive film (its state and entry points; kernels in rt_film.hip) and the multi-device
+// film (one frame film on the first device, a pass workspace per shard), error reporting.
 // A synchronous render (render_sync) runs render_one (one device) or render_many (a thread per
 // shard) over the same stages: prepare_part, enqueue_shard, enqueue_readback, fill_stats.
 #include <hip/hip_runtime.h>
@@ -209,6 +210,41 @@ struct rt_film {
   unsigned long long* feat2 = nullptr; // the remodulation albedo's feature words (rt_denoise_albedo)
   int albedo_samples = 0;              // ... and their sample count (0: none)
   double* dn_mem = nullptr;            // ev[2][4] and guide[8] planes of n_pixels doubles
+  bool owned = false;                  // a multi-device film's frame: rt_film_add / load / reset / destroy refuse it
+  hipEvent_t e_order = nullptr;        // ... and its event: a new `last` stream waits for the one before (film_follow)
+};
+
+// A multi-device film (include/rt.h rt_multi_film_*): ONE accumulation state — `frame`, an ordinary
+// one-shard film of the whole image on devices[0] — and per shard k a pass workspace, a stream and
+// events on devices[k].  A pass renders shard k's samples on devices[k] and rt_film_merge_rows_kernel
+// folds the workspace straight into the frame's rows: launched on devices[k] itself, writing the
+// first device's memory (`direct`, as the one-shot resolve does), or, without peer access, on the
+// first device from a copy of the workspace's sums and flags (`stage`).
+struct FilmPart {
+  int device = 0;
+  const rt_device_scene* scene = nullptr;
+  rt_exec ex{};           // shard k of n on devices[k]
+  int tile_rows = 0;
+  bool active = false;    // the shard holds rows of the frame (more devices than row blocks: not all do)
+  bool direct = true;
+  bool own_ws = false;    // (part 0 renders into the frame film's own pass workspace)
+  char* ws = nullptr;
+  Workspace ws_lay{};
+  char* stage = nullptr;          // first device: the copied sums and flags (copy path)
+  hipStream_t st = nullptr;       // devices[k]: render, then the merge or the copy
+  hipStream_t st_merge = nullptr; // first device: the merge of a copied pass
+  hipEvent_t e_copy = nullptr;    // devices[k]: the copy has landed
+  hipEvent_t e_merge = nullptr;   // the merge is done (on the device whose stream ran it)
+};
+struct rt_multi_film {
+  const rt_multi_scene* scene = nullptr;
+  rt_film* frame = nullptr;
+  std::vector<FilmPart> parts;
+  hipStream_t st_frame = nullptr;  // first device: waits for every merge; the frame film's `last`
+  hipEvent_t e_frame = nullptr;    // first device: what was enqueued on the frame before a pass
+  bool single = false;             // one shard merged on its own stream: that stream is st_frame, no events
+  int64_t copies = 0;              // shard passes that went through the staging copy so far (rt_multi_film_copies)
+  std::mutex mu;
 };
 
 namespace {
@@ -777,6 +813,23 @@ void film_destroy(rt_film* f) {
   }
   delete f;
 }
+// A multi-device film's frame is read like any film, but only the multi film adds to it, loads,
+// resets and destroys it (rt_multi_film_*): rt_film_add / load / reset / destroy refuse it
+int refuse_owned(const rt_film* f, const char* call) {
+  if (f->owned) return fail(RT_E_INVALID, "%s: the film is a multi-device film's frame (use rt_multi_film_*)", call);
+  return RT_OK;
+}
+// Before work on `st`, which then becomes the stream the synchronous calls run behind (`last`).  A
+// plain film's calls are ordered by the caller: nothing to do.  A multi-device film's frame is
+// filled by merges the caller has no stream for, so there a new stream first waits for the one
+// before it (which has waited for the merges)
+int film_follow(rt_film* f, hipStream_t st) {
+  if (f->e_order && st != f->last) {
+    HIP_TRY(hipEventRecord(f->e_order, f->last));
+    HIP_TRY(hipStreamWaitEvent(st, f->e_order, 0));
+  }
+  return RT_OK;
+}
 // the film's totals as one-shot kernel parameters of N samples: what rt_resolve_kernel reads
 template <class R>
 int film_resolve(const rt_film* f, void* d_out, hipStream_t st) {
@@ -1033,12 +1086,14 @@ int rt_film_create(const rt_device_scene* s, const rt_camera_settings* cs, uint6
 }
 
 int rt_film_destroy(rt_film* f) {
+  if (f)
+    if (int rc = refuse_owned(f, "rt_film_destroy")) return rc;
   film_destroy(f);
   return RT_OK;
 }
 
-int rt_film_reset(rt_film* f) {
-  if (!f) return fail(RT_E_INVALID, "null argument");
+namespace {
+int film_reset(rt_film* f) {
   std::lock_guard<std::mutex> lock(f->mu);
   HIP_TRY(hipSetDevice(f->scene->device));
   HIP_TRY(hipMemsetAsync(f->mem, 0, f->state_span, f->last));
@@ -1047,9 +1102,17 @@ int rt_film_reset(rt_film* f) {
   f->passes = 0;
   return RT_OK;
 }
+}  // namespace
+
+int rt_film_reset(rt_film* f) {
+  if (!f) return fail(RT_E_INVALID, "null argument");
+  if (int rc = refuse_owned(f, "rt_film_reset")) return rc;
+  return film_reset(f);
+}
 
 int rt_film_add(rt_film* f, int32_t n_samples, void* hip_stream) {
   if (!f) return fail(RT_E_INVALID, "null argument");
+  if (int rc = refuse_owned(f, "rt_film_add")) return rc;
   if (n_samples <= 0) return fail(RT_E_INVALID, "a pass adds at least one sample (%d)", n_samples);
   std::lock_guard<std::mutex> lock(f->mu);
   if (f->samples + n_samples > RT_FILM_MAX_SAMPLES)
@@ -1074,7 +1137,17 @@ int rt_film_add(rt_film* f, int32_t n_samples, void* hip_stream) {
 
 int rt_film_resolve(const rt_film* f, void* d_out_rgb, void* hip_stream) {
   if (!f || !d_out_rgb) return fail(RT_E_INVALID, "null argument");
-  return film_resolve_any(f, d_out_rgb, (hipStream_t)hip_stream);
+  if (!f->owned) return film_resolve_any(f, d_out_rgb, (hipStream_t)hip_stream);  // (ordered by the caller)
+  // A multi-device film's frame: the caller has no stream to order this read against the merges
+  // with.  The stream first waits for the frame's last stream (which has waited for the merges) and
+  // becomes the last itself, so the next pass's merges wait for this read (multi_film_pass)
+  rt_film* g = const_cast<rt_film*>(f);
+  std::lock_guard<std::mutex> lock(g->mu);
+  HIP_TRY(hipSetDevice(g->scene->device));
+  if (int rc = film_follow(g, (hipStream_t)hip_stream)) return rc;
+  if (int rc = film_resolve_any(g, d_out_rgb, (hipStream_t)hip_stream)) return rc;
+  g->last = (hipStream_t)hip_stream;
+  return RT_OK;
 }
 
 int rt_film_read(const rt_film* f, void* host_out_rgb) {
@@ -1152,8 +1225,8 @@ int rt_film_save(const rt_film* f, void* host_buf, int64_t cap) {
   return RT_OK;
 }
 
-int rt_film_load(rt_film* f, const void* host_buf, int64_t bytes) {
-  if (!f || !host_buf) return fail(RT_E_INVALID, "null argument");
+namespace {
+int film_load(rt_film* f, const void* host_buf, int64_t bytes) {
   std::lock_guard<std::mutex> lock(f->mu);
   if (bytes < (int64_t)sizeof(FilmHeader)) return fail(RT_E_INVALID, "not a saved film (%lld bytes)", (long long)bytes);
   FilmHeader h;
@@ -1184,6 +1257,237 @@ int rt_film_load(rt_film* f, const void* host_buf, int64_t bytes) {
   f->passes = h.passes;
   return RT_OK;
 }
+}  // namespace
+
+int rt_film_load(rt_film* f, const void* host_buf, int64_t bytes) {
+  if (!f || !host_buf) return fail(RT_E_INVALID, "null argument");
+  if (int rc = refuse_owned(f, "rt_film_load")) return rc;
+  return film_load(f, host_buf, bytes);
+}
+
+// ---- multi-device film
+
+namespace {
+
+void multi_film_destroy(rt_multi_film* F) {
+  if (!F) return;
+  const int dev0 = F->scene->devices[0];
+  for (FilmPart& p : F->parts)
+    if (p.st && hipSetDevice(p.device) == hipSuccess) (void)hipStreamSynchronize(p.st);
+  (void)hipSetDevice(dev0);
+  for (FilmPart& p : F->parts)
+    if (p.st_merge) (void)hipStreamSynchronize(p.st_merge);
+  if (F->st_frame) (void)hipStreamSynchronize(F->st_frame);
+  if (F->frame && F->frame->e_order) (void)hipEventDestroy(F->frame->e_order);
+  film_destroy(F->frame);  // (waits for its last stream, which may be st_frame: before that goes)
+  for (FilmPart& p : F->parts) {
+    (void)hipSetDevice(p.device);
+    if (p.direct && p.e_merge) (void)hipEventDestroy(p.e_merge);
+    if (p.e_copy) (void)hipEventDestroy(p.e_copy);
+    if (p.st) (void)hipStreamDestroy(p.st);
+    if (p.own_ws) (void)hipFree(p.ws);
+    (void)hipSetDevice(dev0);
+    if (!p.direct && p.e_merge) (void)hipEventDestroy(p.e_merge);
+    if (p.st_merge) (void)hipStreamDestroy(p.st_merge);
+    (void)hipFree(p.stage);
+  }
+  if (F->e_frame) (void)hipEventDestroy(F->e_frame);
+  if (F->st_frame && !F->single) (void)hipStreamDestroy(F->st_frame);
+  delete F;
+}
+
+// everything enqueued on every part, on the first device's merge streams and on the frame is done
+int multi_film_wait(rt_multi_film* F) {
+  for (FilmPart& p : F->parts) {
+    HIP_TRY(hipSetDevice(p.device));
+    HIP_TRY(hipStreamSynchronize(p.st));
+  }
+  HIP_TRY(hipSetDevice(F->scene->devices[0]));
+  for (FilmPart& p : F->parts)
+    if (p.st_merge) HIP_TRY(hipStreamSynchronize(p.st_merge));
+  HIP_TRY(hipStreamSynchronize(F->st_frame));
+  std::lock_guard<std::mutex> lock(F->frame->mu);
+  if (F->frame->last != F->st_frame) HIP_TRY(hipStreamSynchronize(F->frame->last));
+  return RT_OK;
+}
+
+// One pass: shard k's samples [N, N + n) on devices[k] and their merge into the frame's rows, every
+// shard enqueued without waiting for another.  Ordered by events alone: a merge follows its render
+// (stream order; on the copy path the first device's merge stream waits for the copy) and what
+// was enqueued on the frame before this pass (e_frame); the frame's stream waits for every merge;
+// the part's next pass (its workspace memset first) waits for its merge.
+int multi_film_pass(rt_multi_film* F, int n_samples) {
+  rt_film* fr = F->frame;
+  const int dev0 = F->scene->devices[0];
+  rt_camera_settings cs = fr->cs;
+  cs.samples_per_pixel = n_samples;
+  // (st_frame itself carries only waits and the work of synchronous calls, which has finished:
+  // there is something to wait for only after a call that put a stream of the caller's in its place)
+  const bool after_frame = fr->last != F->st_frame;
+  if (after_frame) {
+    HIP_TRY(hipSetDevice(dev0));
+    HIP_TRY(hipEventRecord(F->e_frame, fr->last));
+  }
+  for (FilmPart& p : F->parts) {
+    if (!p.active) continue;
+    HIP_TRY(hipSetDevice(p.device));
+    if (!p.direct) HIP_TRY(hipStreamWaitEvent(p.st, p.e_merge, 0));  // (a direct merge ran on p.st itself)
+    RenderCall c;  // as rt_film_add's: the sums stay in the workspace
+    c.ws = p.ws, c.ws_cap = p.ws_lay.bytes;
+    c.lone = true;
+    c.sample0 = (int)fr->samples;
+    c.resolve = false;
+    if (int rc = render_any(p.scene, &cs, fr->seed, &p.ex, fr->f32, c, p.st)) return rc;
+    const char* src = p.ws;
+    hipStream_t ms = p.st;
+    if (!p.direct) {
+      HIP_TRY(hipMemcpyPeerAsync(p.stage, dev0, p.ws, p.device, p.ws_lay.off_ctr, p.st));  // sums and flags
+      HIP_TRY(hipEventRecord(p.e_copy, p.st));
+      ++F->copies;
+      HIP_TRY(hipSetDevice(dev0));
+      HIP_TRY(hipStreamWaitEvent(p.st_merge, p.e_copy, 0));
+      src = p.stage, ms = p.st_merge;
+    }
+    if (after_frame) HIP_TRY(hipStreamWaitEvent(ms, F->e_frame, 0));
+    if (rt_film_launch_merge_rows(fr->total, fr->flags, fr->q, (const unsigned long long*)src,
+                                  (const unsigned int*)(src + p.ws_lay.off_flag), fr->width, fr->height, p.tile_rows,
+                                  p.ex.n_shards, p.ex.shard, p.ex.row_block, fr->acc_words, n_samples, ms))
+      return fail(RT_E_HIP, "merge launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (!F->single) HIP_TRY(hipEventRecord(p.e_merge, ms));
+  }
+  if (!F->single) {
+    HIP_TRY(hipSetDevice(dev0));
+    for (FilmPart& p : F->parts)
+      if (p.active) HIP_TRY(hipStreamWaitEvent(F->st_frame, p.e_merge, 0));
+  }
+  fr->last = F->st_frame;
+  return RT_OK;
+}
+
+}  // namespace
+
+int rt_multi_film_create(const rt_multi_scene* m, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex,
+                         rt_multi_film** out) {
+  if (!m || !cs || !ex || !out) return fail(RT_E_INVALID, "null argument");
+  *out = nullptr;
+  if (ex->n_devices != 0) return fail(RT_E_INVALID, "a multi-device film renders on the scene's devices (n_devices = 0)");
+  if (ex->n_shards != 1) return fail(RT_E_INVALID, "a multi-device film holds the whole image (n_shards must be 1)");
+  const int n = (int)m->devices.size(), dev0 = m->devices[0];
+  std::unique_ptr<rt_multi_film, void (*)(rt_multi_film*)> F(new rt_multi_film(), multi_film_destroy);
+  F->scene = m;
+  // the frame: an ordinary one-shard film of the whole image on the first device (its checks are
+  // this call's: camera, flags, no 8-bit encoding)
+  rt_exec e1 = *ex;
+  e1.device = dev0;
+  if (int rc = rt_film_create(m->scenes[0], cs, seed, &e1, &F->frame)) return rc;
+  rt_film* fr = F->frame;
+  fr->owned = true;
+  HIP_TRY(hipSetDevice(dev0));
+  HIP_TRY(hipDeviceSynchronize());  // (the frame's zeroing: the streams below do not wait for the null stream)
+  HIP_TRY(hipStreamCreateWithFlags(&F->st_frame, hipStreamNonBlocking));
+  HIP_TRY(hipEventCreateWithFlags(&F->e_frame, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&fr->e_order, hipEventDisableTiming));
+  fr->last = F->st_frame;
+  // RT_AMD_COPY_SHARDS (experiments and tests, as rt_multi_render's): bit k puts shard k on the path
+  // a device without peer access takes, so one GPU exercises it
+  unsigned long long copy_mask = 0;
+  if (const char* e = rt_knob("RT_AMD_COPY_SHARDS")) copy_mask = (unsigned long long)strtoll(e, nullptr, 0);
+  F->parts.resize(n);
+  for (int k = 0; k < n; ++k) {
+    FilmPart& p = F->parts[k];
+    p.device = m->devices[k];
+    p.scene = m->scenes[m->scene_of[k]];
+    p.ex = fr->ex;  // (planned to run alone, like a film's pass)
+    p.ex.device = p.device;
+    if (n > 1) p.ex.n_shards = n, p.ex.shard = k;
+    p.tile_rows = rt_host_shard_rows(fr->height, &p.ex);
+    p.active = rt_film_block_span(0, fr->width, fr->height, p.ex.n_shards, p.ex.shard, p.ex.row_block).n_pixels > 0;
+    p.direct = m->peer_ok[m->scene_of[k]] && !((copy_mask >> k) & 1ull);
+    p.ws_lay = workspace_layout((size_t)p.tile_rows * fr->width, fr->acc_words);
+    if (int rc = ensure_precisions(p.scene, prec_bit(fr->f32))) return rc;
+    HIP_TRY(hipSetDevice(p.device));
+    HIP_TRY(hipStreamCreateWithFlags(&p.st, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&p.e_copy, hipEventDisableTiming));
+    if (k == 0 && p.ws_lay.bytes <= fr->ws_lay.bytes) {
+      p.ws = fr->ws;  // the frame film never adds a pass of its own: its workspace is shard 0's
+    } else {
+      HIP_TRY(hipMalloc((void**)&p.ws, p.ws_lay.bytes));
+      p.own_ws = true;
+    }
+    if (!p.direct) {
+      HIP_TRY(hipSetDevice(dev0));
+      HIP_TRY(hipMalloc((void**)&p.stage, p.ws_lay.off_ctr));
+      HIP_TRY(hipStreamCreateWithFlags(&p.st_merge, hipStreamNonBlocking));
+    }
+    HIP_TRY(hipEventCreateWithFlags(&p.e_merge, hipEventDisableTiming));  // on the device that merges
+  }
+  if (n == 1 && F->parts[0].direct) {
+    // a list of one device: render and merge follow one another on one stream, as a plain film's
+    // pass does; that stream is the frame's, and a pass records and waits for no event
+    HIP_TRY(hipSetDevice(dev0));
+    HIP_TRY(hipStreamDestroy(F->st_frame));
+    F->st_frame = fr->last = F->parts[0].st;
+    F->single = true;
+  }
+  *out = F.release();
+  return RT_OK;
+}
+
+int rt_multi_film_destroy(rt_multi_film* f) {
+  multi_film_destroy(f);
+  return RT_OK;
+}
+
+int rt_multi_film_reset(rt_multi_film* f) {
+  if (!f) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(f->mu);
+  if (int rc = multi_film_wait(f)) return rc;
+  return film_reset(f->frame);
+}
+
+int rt_multi_film_add(rt_multi_film* f, int32_t n_samples) {
+  if (!f) return fail(RT_E_INVALID, "null argument");
+  if (n_samples <= 0) return fail(RT_E_INVALID, "a pass adds at least one sample (%d)", n_samples);
+  std::lock_guard<std::mutex> lock(f->mu);
+  rt_film* fr = f->frame;
+  std::lock_guard<std::mutex> frame_lock(fr->mu);
+  if (fr->samples + n_samples > RT_FILM_MAX_SAMPLES)
+    return fail(RT_E_INVALID, "a film holds at most 2^24 samples per pixel (%lld + %d)", (long long)fr->samples, n_samples);
+  if (int rc = multi_film_pass(f, n_samples)) return rc;
+  fr->samples += n_samples;
+  fr->passes += 1;
+  return RT_OK;
+}
+
+int rt_multi_film_load(rt_multi_film* f, const void* host_buf, int64_t bytes) {
+  if (!f || !host_buf) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(f->mu);
+  if (int rc = multi_film_wait(f)) return rc;
+  return film_load(f->frame, host_buf, bytes);
+}
+
+int rt_multi_film_frame(rt_multi_film* f, rt_film** frame) {
+  if (!f || !frame) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(f->mu);
+  *frame = f->frame;
+  if (int rc = multi_film_wait(f)) return rc;
+  int status = 0;
+  for (const rt_device_scene* s : f->scene->scenes) {
+    int ps = 0;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMemcpy(&ps, s->status, sizeof(int), hipMemcpyDeviceToHost));
+    status |= ps;
+  }
+  if (status) return fail(RT_E_STACK, "BVH traversal stack overflow");
+  return RT_OK;
+}
+
+int rt_multi_film_copies(const rt_multi_film* f, int64_t* n) {
+  if (!f || !n) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(const_cast<rt_multi_film*>(f)->mu);
+  *n = f->copies;
+  return RT_OK;
+}
 
 // ---- first-hit features and the denoiser
 
@@ -1201,6 +1505,7 @@ int rt_denoise_features(rt_film* f, int32_t n_feat, void* hip_stream) {
   if (!f->feat) HIP_TRY(hipMalloc((void**)&f->feat, f->n_pixels * rt_feat_words(!f->f32) * sizeof(long long)));
   f->feat_samples = 0;
   hipStream_t st = (hipStream_t)hip_stream;
+  if (int rc = film_follow(f, st)) return rc;
   if (int rc = f->f32 ? film_features<float>(f, f->feat, n_feat, st) : film_features<double>(f, f->feat, n_feat, st)) return rc;
   f->feat_samples = n_feat;
   f->last = st;
@@ -1219,6 +1524,7 @@ int rt_denoise_albedo(rt_film* f, int32_t n_albedo, void* hip_stream) {
   if (!f->feat2) HIP_TRY(hipMalloc((void**)&f->feat2, f->n_pixels * rt_feat_words(!f->f32) * sizeof(long long)));
   f->albedo_samples = 0;
   hipStream_t st = (hipStream_t)hip_stream;
+  if (int rc = film_follow(f, st)) return rc;
   if (int rc = f->f32 ? film_features<float>(f, f->feat2, n_albedo, st) : film_features<double>(f, f->feat2, n_albedo, st))
     return rc;
   f->albedo_samples = n_albedo;
@@ -1262,6 +1568,8 @@ int rt_denoise_film(rt_film* f, const rt_denoise_params* p, void* d_out_rgb, voi
   if (p) dp = *p;
   std::lock_guard<std::mutex> lock(f->mu);
   if (int rc = denoise_check(f, &dp)) return rc;
+  HIP_TRY(hipSetDevice(f->scene->device));
+  if (int rc = film_follow(f, (hipStream_t)hip_stream)) return rc;
   if (int rc = film_denoise(f, &dp, d_out_rgb, (hipStream_t)hip_stream)) return rc;
   f->last = (hipStream_t)hip_stream;
   return RT_OK;

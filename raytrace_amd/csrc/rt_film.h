@@ -66,6 +66,26 @@ RT_FILM_FN double rt_film_rel_error(double q, double T, long long N, int K) {
   return se / (M > RT_FILM_FLOOR ? M : RT_FILM_FLOOR);
 }
 
+// A shard's row block inside its tile and inside the whole frame (the rt_exec interleave,
+// include/rt.h rt_shard_row: tile row t is global row ((t / row_block) n_shards + shard) row_block +
+// t % row_block).  Tile block b is a contiguous run of pixels in both: it starts at tile pixel
+// b row_block width and at frame pixel (b n_shards + shard) row_block width.  n_pixels counts the
+// rows that lie inside the frame: the last block may be cut short by `height`, a padding block has 0.
+struct rt_film_span {
+  long long tile_pixel, frame_pixel;
+  int n_pixels;
+};
+RT_FILM_FN rt_film_span rt_film_block_span(int b, int width, int height, int n_shards, int shard, int row_block) {
+  const long long g0 = ((long long)b * n_shards + shard) * row_block;  // the block's first global row
+  const long long left = (long long)height - g0;
+  const int rows = left <= 0 ? 0 : (left < row_block ? (int)left : row_block);
+  rt_film_span s;
+  s.tile_pixel = (long long)b * row_block * width;
+  s.frame_pixel = g0 * width;
+  s.n_pixels = rows * width;
+  return s;
+}
+
 // ---- launchers (rt_film.hip); device pointers, asynchronous on `stream`, 0 or -1
 // pixels per workgroup of both kernels (one partial of the noise figure per workgroup)
 #define RT_FILM_TILE 512
@@ -75,6 +95,13 @@ inline int rt_film_blocks(long long n_pixels) { return (int)((n_pixels + RT_FILM
 int rt_film_launch_merge(unsigned long long* total, unsigned int* flags, double* q, const unsigned long long* pass,
                          const unsigned int* pass_flags, long long n_pixels, int acc_words, int n_samples,
                          void* stream);
+// The merge of shard (n_shards, shard, row_block)'s pass (pass / pass_flags: its tile of tile_rows =
+// rt_shard_rows rows) into the totals of a whole width x height frame (total / flags / q), block by
+// block through rt_film_block_span.  It touches the frame pixels of the shard's rows and nothing
+// else (no slack is needed or written), so merges of different shards into one frame may overlap.
+int rt_film_launch_merge_rows(unsigned long long* total, unsigned int* flags, double* q, const unsigned long long* pass,
+                              const unsigned int* pass_flags, int width, int height, int tile_rows, int n_shards, int shard,
+                              int row_block, int acc_words, int n_samples, void* stream);
 // map (float per tile pixel) may be null; partial_sum / partial_cnt: rt_film_blocks(n_pixels)
 // entries, the sum of r^2 and the number of pixels that count per workgroup, to be added in index
 // order.  Tile rows whose global row (the rt_exec interleave) is >= height are padding

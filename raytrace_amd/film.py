@@ -13,7 +13,8 @@ of a, b, c samples give exactly the image of `raytrace` at a + b + c samples per
 
 `raytrace_until` is that loop as one call.  `noise_from_sums` restates the estimator in numpy.
 `film.denoised()` is the image filtered for a preview and `film.features()` its guide buffers
-(raytrace_amd.denoise).
+(raytrace_amd.denoise).  `MultiFilm(world, settings, seed, devices=[0, 1, ...])` is the same film
+rendered by several GPUs into one frame; `raytrace_until(..., devices=[...])` runs on it.
 """
 from __future__ import annotations
 
@@ -44,25 +45,37 @@ class Film:
         self.handle = None
         self._own_scene = not isinstance(world, DeviceScene)
         self.scene = DeviceScene(world, device) if self._own_scene else world
+        self._create(settings, seed, precision, self.scene.device, dict(n_shards=n_shards, shard=shard, row_block=row_block))
+
+    def _create(self, settings, seed, precision, device, exec_kw):
+        """The part of construction every kind of film shares: the camera and rt_exec records, the
+        library handle(s) from `_new_film(seed64)` (the film's own scene is closed again if that
+        fails) and the attributes the reading methods use."""
+        self.device = device  # where the state lives (torch buffers of noise_map)
         self.settings = settings
         self.precision = precision
-        self.dtype = _lib.dtype_of(precision)
-        self._cs = _lib.camera_struct(settings)
-        self._ex = _lib.exec_struct(device=self.scene.device, n_shards=n_shards, shard=shard, row_block=row_block,
-                                    precision=precision)
-        h = ctypes.c_void_p()
         try:
-            _lib.check(self._lib.rt_film_create(self.scene.handle, ctypes.byref(self._cs), _seed64(seed),
-                                                ctypes.byref(self._ex), ctypes.byref(h)))
+            self.dtype = _lib.dtype_of(precision)
+            self._cs = _lib.camera_struct(settings)
+            self._ex = _lib.exec_struct(device=device, precision=precision, **exec_kw)
+            self._new_film(_seed64(seed))
         except Exception:
             if self._own_scene:
                 self.scene.close()
             raise
-        self.handle = h
         info = self.info()
         self.shape = (info["rows"], info["width"], 3)
         self._feature_samples = 0  # n of the feature words on the device (0: not computed)
         self._albedo_samples = 0   # ... of the remodulation albedo (0: none)
+
+    def _new_film(self, seed64):
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.rt_film_create(self.scene.handle, ctypes.byref(self._cs), seed64, ctypes.byref(self._ex),
+                                            ctypes.byref(h)))
+        self.handle = h
+
+    def _ready(self):
+        """Before a read.  A plain film's reads follow its last add by stream order: nothing to do."""
 
     def info(self) -> dict:
         st = _lib.RtFilmInfo()
@@ -86,12 +99,14 @@ class Film:
     def image(self, out: np.ndarray | None = None) -> np.ndarray:
         """The mean of the samples so far: (rows, width, 3) linear RGB, as `raytrace` at .spp."""
         from .ray import _out_buffer
+        self._ready()
         out = _out_buffer(out, self.shape, self.dtype)
         _lib.check(self._lib.rt_film_read(self.handle, out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
     def noise(self) -> float:
         """sqrt(mean r^2) of the per-pixel relative standard error r (noise_map); needs two passes."""
+        self._ready()
         v = ctypes.c_double()
         _lib.check(self._lib.rt_film_noise(self.handle, None, ctypes.byref(v)))
         return v.value
@@ -100,7 +115,8 @@ class Film:
         """(rows, width) float32: each pixel's relative standard error of its mean R + G + B against
         max(mean, 3/256); NaN for pixels with a non-finite sample and a shard's padding rows."""
         import torch
-        m = torch.empty(self.shape[0] * self.shape[1], dtype=torch.float32, device=f"cuda:{self.scene.device}")
+        self._ready()
+        m = torch.empty(self.shape[0] * self.shape[1], dtype=torch.float32, device=f"cuda:{self.device}")
         v = ctypes.c_double()
         _lib.check(self._lib.rt_film_noise(self.handle, ctypes.c_void_p(m.data_ptr()), ctypes.byref(v)))
         return m.cpu().numpy().reshape(self.shape[:2])
@@ -110,6 +126,7 @@ class Film:
         again only when n changes) and its integer words: (rows, width, 8) int64 — albedo RGB, normal
         xyz and the depth sum in units of 2^-32, and the hit count —, in a binary64 film (rows, width,
         16): those, then the next 32 bits of each sum (denoise.features_from_words)."""
+        self._ready()
         if self._feature_samples != int(n):
             self._feature_samples = 0
             _lib.check(self._lib.rt_denoise_features(self.handle, int(n), ctypes.c_void_p(stream_ptr or None)))
@@ -137,6 +154,7 @@ class Film:
         multiplies the result by this better estimate.  Computed once: it does not change as samples
         are added."""
         from .denoise import features_from_words
+        self._ready()
         if self._albedo_samples != int(n):
             self._albedo_samples = 0
             _lib.check(self._lib.rt_denoise_albedo(self.handle, int(n), None))
@@ -159,6 +177,7 @@ class Film:
         from .denoise import params_struct
         from .ray import _out_buffer
         p = params_struct(params, levels=levels)
+        self._ready()
         if self._feature_samples != int(feature_samples):
             self._feature_samples = 0
             _lib.check(self._lib.rt_denoise_features(self.handle, int(feature_samples), None))
@@ -173,6 +192,7 @@ class Film:
 
     def state(self) -> np.ndarray:
         """The film's state as bytes (header, sums, flags, estimator words): see `unpack_state`."""
+        self._ready()
         n = ctypes.c_int64()
         _lib.check(self._lib.rt_film_state_bytes(self.handle, ctypes.byref(n)))
         buf = np.zeros(n.value, np.uint8)
@@ -208,6 +228,85 @@ class Film:
             self.close()
         except Exception:
             pass
+
+
+class MultiFilm(Film):
+    """A film over a list of GPUs of this process (include/rt.h rt_multi_film_*): `Film`'s interface,
+    one frame.  Shard k of every pass renders on devices[k] (rows dealt round-robin in blocks of
+    `row_block`, as `raytrace(..., devices=...)`) and is merged straight into ONE accumulation state
+    on devices[0], which is bit for bit the state of a plain `Film` after the same passes: images,
+    noise figures, feature buffers and denoised images are equal, and `state()` / `restore()`
+    interchange with a plain `Film(..., row_block=row_block)` of the same frame, whatever the device
+    counts.  The feature and albedo passes (first hits only) run on devices[0].  Every reading method
+    first waits for every device (rt_multi_film_frame), so a traversal-stack overflow on any device
+    is raised by whichever is called.
+
+    `world`: a scene description (uploaded to `devices`, default every GPU; freed by close()) or a
+    MultiDeviceScene (the caller's: it must outlive the film).  A device may repeat."""
+
+    def __init__(self, world, settings: CameraSettings, seed, devices=None, precision: str = "f64", row_block: int = 4):
+        from .errors import RtInvalid
+        from .ray import MultiDeviceScene
+        self._lib = _lib.load()
+        self.handle = None   # the frame: an ordinary one-shard film, owned by the multi film
+        self._multi = None
+        self._own_scene = not isinstance(world, MultiDeviceScene)
+        if not self._own_scene and devices is not None and [int(d) for d in devices] != world.devices:
+            raise RtInvalid(f"the scene is resident on devices {world.devices}, not {list(devices)}")
+        if self._own_scene and devices is None:
+            devices = list(range(_lib.check(self._lib.rt_device_count())))
+        self.scene = MultiDeviceScene(world, devices) if self._own_scene else world
+        self.devices = list(self.scene.devices)
+        self._create(settings, seed, precision, self.devices[0], dict(row_block=row_block))
+
+    def _new_film(self, seed64):
+        m = ctypes.c_void_p()
+        _lib.check(self._lib.rt_multi_film_create(self.scene.handle, ctypes.byref(self._cs), seed64, ctypes.byref(self._ex),
+                                                  ctypes.byref(m)))
+        self._multi = m
+        self._frame()
+
+    def _frame(self):
+        """Wait for every device and take the frame handle (rt_multi_film_frame: raises on a
+        traversal-stack overflow on any device)."""
+        h = ctypes.c_void_p()
+        rc = self._lib.rt_multi_film_frame(self._multi, ctypes.byref(h))
+        self.handle = h
+        _lib.check(rc)
+
+    def add(self, n: int):
+        """Enqueue samples [spp, spp + n) of every pixel on every device (asynchronous; returns self)."""
+        _lib.check(self._lib.rt_multi_film_add(self._multi, int(n)))
+        return self
+
+    _ready = _frame  # every read (image, noise, state, features, denoised) reports every device's status
+
+    @property
+    def copied_passes(self) -> int:
+        """Shard passes so far whose sums reached devices[0] through the staging copy (devices
+        without peer access to it; 0 otherwise)."""
+        n = ctypes.c_int64()
+        _lib.check(self._lib.rt_multi_film_copies(self._multi, ctypes.byref(n)))
+        return n.value
+
+    def restore(self, state: np.ndarray):
+        """Load a state saved from a MultiFilm (of any device list) or a plain one-shard Film of the
+        same frame, seed, precision and row_block."""
+        buf = np.ascontiguousarray(state, np.uint8)
+        _lib.check(self._lib.rt_multi_film_load(self._multi, buf.ctypes.data_as(ctypes.c_void_p), buf.size))
+        return self
+
+    def reset(self):
+        _lib.check(self._lib.rt_multi_film_reset(self._multi))
+        return self
+
+    def close(self):
+        if self._multi:
+            self._lib.rt_multi_film_destroy(self._multi)
+            self._multi = None
+            self.handle = None
+            if self._own_scene:
+                self.scene.close()
 
 
 HEADER_DTYPE = np.dtype([("magic", "<u4"), ("version", "<u4"), ("f32", "<i4"), ("width", "<i4"), ("height", "<i4"),
@@ -261,19 +360,21 @@ def noise_from_sums(pass_sums, pass_sizes) -> dict:
 
 
 def raytrace_until(settings: CameraSettings, world, seed, noise: float, batch: int = 16, max_spp: int | None = None,
-                   denoise: bool = False, denoise_params: dict | None = None, **kw):
+                   denoise: bool = False, denoise_params: dict | None = None, devices=None, **kw):
     """Render in passes of `batch` samples until the frame's noise figure (Film.noise) is at most
     `noise` (checked from the second pass on) or `max_spp` samples per pixel are reached (default
     cs_samplesPerPixel; the last pass is cut to fit).  Returns (image, info): the image is
     `raytrace`'s at info["spp"] samples; info has spp, passes, noise (None before two passes) and
     converged.  denoise=True returns the denoised image instead (Film.denoised with denoise_params;
     it needs two passes: max_spp > batch) and keeps the raw one in info["raw"].  kw: Film's
-    precision, device, n_shards, shard, row_block."""
+    precision, device, n_shards, shard, row_block.  `devices`: a list of GPUs that render the passes
+    together (a MultiFilm; kw: precision, row_block); image and info are the one-device call's."""
     if batch <= 0:
         from .errors import RtInvalid
         raise RtInvalid("batch must be positive")
     max_spp = int(settings.cs_samplesPerPixel if max_spp is None else max_spp)
-    with Film(world, settings, seed, **kw) as film:
+    with (Film(world, settings, seed, **kw) if devices is None else
+          MultiFilm(world, settings, seed, devices=devices, **kw)) as film:
         spp, passes, figure, converged = 0, 0, None, False
         while spp < max_spp:
             n = min(batch, max_spp - spp)
