@@ -323,6 +323,7 @@ int render_async(const rt_device_scene* s, const rt_camera_settings* cs, uint64_
   L.lone = c.lone || (ex && (ex->flags & RT_EXEC_SOLO));  // (the caller says this render runs alone)
   L.sample0 = c.sample0;
   L.out_frame_rows = c.frame_rows;
+  L.flat_ring = true;  // (where the scene's class has the ring form: rt_build.cpp rt_host_plan_ring)
   if (const char* e = rt_knob("RT_AMD_POOL_SHIFT")) L.pool_shift = std::max(4, std::min(10, atoi(e)));
   KernelParamsT<R> P;
   std::string err;

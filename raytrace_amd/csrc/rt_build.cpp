@@ -1234,6 +1234,7 @@ int rt_host_render_params(const HostScene& H, int variant, const SceneRecordsT<R
   // (a synchronous call's flat kernel: 64-id pools, rt_api.hip render_async)
   P.pool_shift = L.pool_shift ? L.pool_shift : L.lone && flat ? 6 : 0;
   rt_host_plan_work(P, L.resident_lanes, flat, L.lone);
+  if (L.flat_ring) rt_host_plan_ring(P, variant, L.lone, L.pool_shift, L.resident_lanes);  // (the ring form's plan in place of that one)
   P.trav_exit_pct = f64 ? H.trav_exit_pct64 : H.trav_exit_pct;
   P.out_frame_rows = L.out_frame_rows;
   P.sample0 = L.sample0;
@@ -1367,6 +1368,54 @@ void rt_host_plan_work(KernelParamsT<R>& P, long long resident_lanes, bool two_s
   P.agg_big = agg && spans(n_big);
   P.agg_small = agg && spans(P.n_chunks);
 }
+
+// The ring form of the flat lane loop (rt_trace.h lane_loop_flat_ring): the wave owns a stream of
+// samples, so an item is ONE sample, id = tile pixel x spp + (sample - sample0), pixel-major and
+// sample-minor — open_item's small-item decode with chunk 1 and no big items.  Every (pixel, sample)
+// pair is still one item, rendered once; the Philox counters depend on the pair alone and the sums
+// are integers, so the image is the legacy plan's bit for bit.  A pool of consecutive ids is a
+// contiguous range of the stream.  A wave waits for the queue's returning atomic with all its lanes
+// (the ring is empty when it refills), so pools are large: 1024 ids where frames overlap, 512 for a
+// synchronous call, whose launch ends on the pools the waves still hold (Cornell binary64, overlapped:
+// 4.341 / 4.229 / 4.174 / 4.158 ms with 128 / 256 / 512 / 1024 ids; synchronous: 4.340 / 4.229 /
+// 4.174 with 128 / 256 / 512; profiles/flat_ring) — halved while the resident waves would get fewer
+// than 8 pools each (a small image still spreads over the device) or the pool's pixel span
+// ceil((pool - 1) / spp) + 1 exceeds a slot (RT_RING_AGG_PIX), down to 64.  After rt_host_plan_work
+// (the divisors).  The class: flat, constant textures, the diffuse materials, no media.
+template <class R>
+bool rt_host_plan_ring(KernelParamsT<R>& P, int variant, bool lone, int pool_shift, long long resident_lanes) {
+  P.flat_ring = 0;
+  if (!rt_class_has_ring(rt_class_of(sizeof(R) == 8, variant))) return false;
+  if (const char* e = rt_knob("RT_AMD_FLAT_RING"))
+    if (std::atoi(e) == 0) return false;
+  const long long tile_pixels = (long long)P.tile_rows * P.cam.width;
+  const int spp = P.cam.spp;
+  if (spp <= 0 || tile_pixels <= 0 || tile_pixels * spp > 0x7fffff00LL) return false;
+  const bool pool_given = pool_shift >= 4;  // (LaunchInputs::pool_shift)
+  int shift = pool_given ? pool_shift : lone ? 9 : 10;
+  auto spans = [&](int s) { return ((1 << s) - 1 + spp - 1) / spp + 1 <= RT_RING_AGG_PIX; };
+  const long long waves = resident_lanes / 64;
+  auto spreads = [&](int s) { return waves <= 0 || (8ll << s) * waves <= tile_pixels * spp; };
+  while (!pool_given && shift > 6 && !(spans(shift) && spreads(shift))) --shift;
+  P.pool_shift = shift;
+  P.chunk = 1;
+  P.n_chunks = spp;
+  P.big_chunk = 1;
+  P.n_big_chunks = 0;
+  P.big_items = 0;
+  P.small_start = 0;
+  P.div_big = rt_host_fastdiv(1u);
+  P.div_small = rt_host_fastdiv((uint32_t)spp);
+  P.n_items = (int)(tile_pixels * spp);
+  bool agg = tile_pixels < (1ll << 24);  // the item's aggregation code shares its tile-pixel word
+  if (const char* env = rt_knob("RT_AMD_AGG")) agg = agg && std::atoi(env) != 0;
+  P.agg_big = 0;
+  P.agg_small = agg && spans(shift);
+  P.flat_ring = 1;
+  return true;
+}
+template bool rt_host_plan_ring<float>(KernelParamsT<float>&, int, bool, int, long long);
+template bool rt_host_plan_ring<double>(KernelParamsT<double>&, int, bool, int, long long);
 
 template int rt_host_make_params<float>(const rt_camera_settings*, uint64_t, const rt_exec*, KernelParamsT<float>&,
                                         std::string&);

@@ -75,6 +75,16 @@
 #ifndef RT_AGG_PIX_BVH
 #define RT_AGG_PIX_BVH 5  // n >= 32 (the BVH kernels' LDS is node staging too)
 #endif
+// The ring form of the flat lane loop (rt_trace.h lane_loop_flat_ring; the constant-texture diffuse
+// flat class): a wave's LDS holds a ring of 64 prepared camera rays (origin, direction: 6 reals,
+// and 4 words: the time's Philox word, pixel, sample, tagged tile pixel) in place of most of the
+// wide aggregation slots.  Its items are single samples, so a pool of consecutive ids spans
+// ceil((pool - 1) / spp) + 1 pixels: narrower slots (binary64 6 x 8 pixels + ring = 6448 B per wave
+// against the legacy loop's 7448; FP32 5 x 8 + ring = 3560 against 3752)
+#define RT_RING_LANES 64
+#define RT_RING_AGG_PIX 8
+#define RT_RING_AGG_SLOTS_F64 6
+#define RT_RING_AGG_SLOTS_F32 5
 #ifndef RT_BIG_CHUNK_MAX
 #define RT_BIG_CHUNK_MAX 16  // samples per big work item at most, synchronous calls (rt_build.cpp rt_host_plan_work)
 #endif
@@ -362,6 +372,10 @@ struct KernelParamsT {
   // the camera has a defocus disk (cam.disk_u or cam.disk_v is not zero): camera_ray's test as one
   // scalar integer compare instead of six binary64 VALU compares on scalar operands
   int cam_defocus;
+  // the work plan is the ring form's (rt_build.cpp rt_host_plan_ring): every item is ONE sample, id =
+  // tile pixel x spp + sample (one item size: big_items 0, chunk 1, n_chunks = spp), and the launch
+  // runs rt_render_kernel_ring (rt_render_kernel.h).  0: items are chunks, the legacy loops
+  int flat_ring;
 };
 using DevMaterial = DevMaterialT<float>;
 using DevTexture = DevTextureT<float>;
@@ -465,6 +479,10 @@ struct LaunchInputs {
   bool lone = false;             // a synchronous call's one launch (rt_api.hip render_async)
   int sample0 = 0, out_frame_rows = 0;
   int pool_shift = 0;            // 4-10: KernelParams::pool_shift whatever the plan would choose
+  // the caller launches the ring form of the flat loop where the class has one (rt_api.hip renders;
+  // env RT_AMD_FLAT_RING=0, experiments, keeps the legacy loop).  The host emulator and the feature
+  // pass, which run the legacy loop, leave it false
+  bool flat_ring = false;
 };
 // The whole argument block of one render of H by the kernel class of `variant`, but for the
 // workspace and output pointers (out, status, accum, nanflag, counter: left null): P zeroed, then
@@ -483,6 +501,10 @@ int rt_host_match_target(const HostScene& H, int variant, KernelParamsT<R>& P);
 // work decomposition (rt_build.cpp): chunk so that items >= ~8 x resident lanes
 template <class R>
 void rt_host_plan_work(KernelParamsT<R>& P, long long resident_lanes, bool two_sizes, bool lone = false);  // two_sizes: flat kernel
+// the ring form's plan (KernelParams::flat_ring), or false (P's plan untouched): the variant's class
+// has no ring form or the samples of the tile do not fit an item id
+template <class R>
+bool rt_host_plan_ring(KernelParamsT<R>& P, int variant, bool lone, int pool_shift = 0, long long resident_lanes = 0);
 FastDiv rt_host_fastdiv(uint32_t d);
 // the 8-bit code thresholds of the output epilogue (rt_build.cpp): thr[k] = the smallest binary64
 // x in [0, 1] whose code min(255, floor(256 transfer(x))) is >= k (k = 1..255; thr[0] = 0)

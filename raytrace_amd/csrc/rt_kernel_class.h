@@ -177,6 +177,24 @@ constexpr size_t rt_class_lds_bytes(bool f64, KernelClass c, int stack_depth, in
          (c.var == RT_VAR_FLAT ? 0 : (size_t)(stack_depth + 1) * rt_class_block(f64, c) * sizeof(int) + (size_t)lds_nodes * 64);
 }
 
+// The ring form of the flat lane loop (rt_render_kernel.h rt_render_kernel_ring, rt_trace.h
+// lane_loop_flat_ring): one class has it, in both precisions — flat, constant textures, the diffuse
+// materials, no media (the Cornell box) — as a kernel of its own beside the class's legacy one, at
+// the class's occupancy.  LDS of its one-wave workgroup: the ring's 64 rays (6 reals and 4 words
+// each), then the aggregation slots (rt_internal.h RT_RING_*); never more than the legacy kernel's.
+constexpr KernelClass rt_ring_class() { return KernelClass{RT_VAR_FLAT, 0, 0, false, false, 0, false}; }
+constexpr bool rt_class_has_ring(KernelClass c) {
+  return c.var == RT_VAR_FLAT && c.tex == 0 && c.media == 0 && !c.mats && !c.inst;
+}
+constexpr int rt_ring_agg_slots(bool f64) { return f64 ? RT_RING_AGG_SLOTS_F64 : RT_RING_AGG_SLOTS_F32; }
+constexpr int rt_ring_agg_bytes(bool f64) { return rt_ring_agg_slots(f64) * (RT_RING_AGG_PIX * rt_acc_words(f64) * 8 + 2 * 4); }
+constexpr int rt_ring_ray_bytes(bool f64) { return RT_RING_LANES * (6 * (f64 ? 8 : 4) + 4 * 4); }
+constexpr size_t rt_ring_lds_bytes(bool f64) { return (size_t)rt_ring_ray_bytes(f64) + rt_ring_agg_bytes(f64); }
+static_assert(RT_BLOCK == RT_RING_LANES, "the ring belongs to a one-wave workgroup");
+static_assert(rt_ring_lds_bytes(false) <= rt_class_fixed_lds(false, rt_ring_class()) &&
+                  rt_ring_lds_bytes(true) <= rt_class_fixed_lds(true, rt_ring_class()),
+              "the ring form's LDS must not exceed the legacy kernel's (same workgroups per CU)");
+
 // Kernels built without MachineLICM (rt_kernel_nl.hip / rt_kernel64_nl.hip, compiled with
 // -mllvm -disable-machine-licm): the pass hoists the loop's binary64 constants (log, sincos and
 // texture polynomial coefficients, ...) out of the persistent lane loop into ~20-90 VGPRs, so the

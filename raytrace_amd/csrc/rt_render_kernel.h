@@ -266,6 +266,40 @@ struct WaveWork {
     }
     if (bad) atomicOr(kp().nanflag + tp, 1u);
   }
+  // The ring form (rt_trace.h lane_loop_flat_ring) commits every sample, from the few lanes whose
+  // path has just ended, so the slot's pixel is resolved where the id is opened, by the whole
+  // wave: the code carries the slot + 1 in bits 24-26 and the pixel's offset within the slot in bits
+  // 27-31 (tag_ring), and the commit adds the sample's words without reading the header or testing
+  // them for zero (one exec region instead of seven)
+  __device__ __forceinline__ int tag_ring(int tp, int slot) const {
+    static_assert(kSlots <= 7 && kPix <= 32, "tag_ring: 3 bits of slot + 1, 5 bits of pixel offset");
+    if (slot < 0) return tp;
+    return (int)((uint32_t)tp | (uint32_t)((slot + 1) | ((tp - hdr[kSlots + slot]) << 3)) << 24);
+  }
+  // counts an id that has no sample (a padding row, a render without depth) off its pool's slot
+  __device__ __forceinline__ void skip_ring(bool c, int tpk) {
+    if (!c || !aggregating()) return;
+    const int code = (int)((uint32_t)tpk >> 24) & 7;
+    if (code) __hip_atomic_fetch_add(hdr + code - 1, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  __device__ __forceinline__ void commit_ring(int tpk, const Acc& A, bool bad) {
+    const uint32_t code = aggregating() ? (uint32_t)tpk >> 24 : 0u;
+    const int tp = code ? tpk & 0xffffff : tpk;
+    if (code == 0u) {
+      direct(tp, A);
+    } else {
+      const int s = (int)(code & 7u) - 1;
+      unsigned long long* w = slots + s * AggGeom<kSlots, kPix>::kWords + (int)(code >> 3) * RT_ACC_WORDS(real);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) lds_add(w + k, (unsigned long long)A.hi[k]);
+#if RT_F64
+#pragma unroll
+      for (int k = 0; k < 3; ++k) lds_add(w + 3 + k, A.lo[k]);
+#endif
+      __hip_atomic_fetch_add(hdr + s, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // no return
+    }
+    if (bad) atomicOr(kp().nanflag + tp, 1u);
+  }
   // add a closed slot's words to `accum` (consecutive pixels: consecutive addresses) and free it
   __device__ __forceinline__ void flush(int s) {
     constexpr int kW = AggGeom<kSlots, kPix>::kWords;
@@ -383,6 +417,24 @@ void rt_render_kernel(KernelParams P) {
   }
   if (overflow) atomicOr(P.status, 1);
 }
+
+#if !RT_TU_NOLICM  // (the main translation unit: rt_ring_class is compiled with MachineLICM)
+// The ring form of rt_ring_class's kernel (rt_trace.h lane_loop_flat_ring; launched when
+// KernelParams::flat_ring): a one-wave workgroup at the class's occupancy floor.  LDS: the ring's
+// rays, then this wave's aggregation slots (rt_kernel_class.h rt_ring_lds_bytes).
+__global__ __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(rt_class_waves(RT_F64, rt_ring_class()))))
+void rt_render_kernel_ring(KernelParams P) {
+  extern __shared__ int smem[];
+  real* ring_od = reinterpret_cast<real*>(smem);
+  uint32_t* ring_meta = reinterpret_cast<uint32_t*>(ring_od + 6 * RT_RING_LANES);
+  unsigned long long* agg = reinterpret_cast<unsigned long long*>(ring_meta + 4 * RT_RING_LANES);
+  constexpr int kAggBytes = rt_ring_agg_bytes(RT_F64);
+  for (int i = (int)__lane_id(); i < kAggBytes / 8; i += 64) agg[i] = 0ull;
+  WaveWork<rt_ring_agg_slots(RT_F64), RT_RING_AGG_PIX, true> work(P, (int)blockIdx.x, (int)gridDim.x, agg);
+  lane_loop_flat_ring(P, work, ring_od, ring_meta);
+  work.finish();
+}
+#endif
 
 #ifndef RT_KERNEL_ONLY  // (register probes of one instantiation: tools/reg_probe.sh)
 #if !RT_TU_NOLICM  // (the main translation unit)
@@ -504,6 +556,11 @@ int rt_launch_render(const KernelParamsT<RT_NS::real>& p, int grid_blocks, int v
   const int block = rt_class_block(RT_F64, c);
   long long need = ((long long)p.n_items + block - 1) / block;
   int grid = need < grid_blocks ? (int)need : grid_blocks;
+  if (p.flat_ring) {  // the ring form's plan (rt_build.cpp rt_host_plan_ring): its kernel, or none
+    if (!rt_class_has_ring(c)) return -1;
+    hipLaunchKernelGGL(rt_render_kernel_ring, dim3(grid), dim3(block), rt_ring_lds_bytes(RT_F64), (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+  }
   size_t lds = rt_class_lds_bytes(RT_F64, c, p.stack_depth, p.lds_nodes);
   hipLaunchKernelGGL(render_kernel_of(variant), dim3(grid), dim3(block), lds, (hipStream_t)stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -1;

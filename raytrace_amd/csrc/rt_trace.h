@@ -6,7 +6,9 @@
 // words (one wave-aggregated atomic per 128 items; rt_render_kernel.h WaveWork, which also sums a
 // pool's items per pixel in LDS before they reach HBM), so every lane stays busy until the queue
 // drains and the tail is one chunk long.  Inside an item a lane
-// regenerates paths: when a path terminates the next sample starts at once.  Per segment:
+// regenerates paths: when a path terminates the next sample starts at once.  (The diffuse flat
+// class's ring form, lane_loop_flat_ring below, gives the samples to the wave instead: an item is
+// one sample and new paths start 64 wide from a ring of prepared rays in LDS.)  Per segment:
 //   1. closest hit: flat sets (class loops and box groups over wave-uniform records), or the
 //      surface set's large-primitive prefix then its BVH (stack in LDS, near child first,
 //      leaves tested once a per-scene share of the lanes hold one), with the reference's
@@ -2050,6 +2052,129 @@ RT_FN int lane_loop_lockstep(const KernelParams& P0, Work& work, const Trav& TW,
   RT_PROF_FLUSH
   return overflow;
 }
+
+#ifndef RT_HOST_EMU
+// The ring form of the flat lockstep loop (KernelParams::flat_ring; rt_kernel_class.h
+// rt_class_has_ring: constant textures, the diffuse materials, no media).  The legacy loop above
+// starts a path where the last one ended: item bookkeeping, open_item and camera_ray_flat run in
+// nearly every iteration for the ~19 of 64 lanes whose path has just ended (a quarter of the
+// loop's clocks, profiles/flat_ring).  Here the samples belong to the WAVE: an item is one sample
+// (rt_build.cpp rt_host_plan_ring), and when the ring of prepared rays in LDS is empty the whole
+// wave claims the next 64 ids of its pool (work.grab, every lane), decodes them (open_item) and
+// makes their camera rays (camera_ray_flat: the same code on the same (pixel, sample), so the same
+// bits) in one full-width pass, and stores them to the ring; padding rows and a render without
+// depth produce no entry.  A lane whose path has ended pops an entry by ballot and mbcnt prefix;
+// if the ring runs dry in the middle of a pop the wave refills and the remaining lanes pop in the
+// same iteration.  Only the refill that meets the end of the queues is narrower than 64 lanes'
+// worth, and the frame's last samples are spread over the wave's lanes by construction (no
+// steal_sample).  A finished sample adds its fixed-point words straight to its pool's aggregation
+// slot (work.commit_ring), so a lane carries no item sums: its state is the ray, T, apdf, the segment
+// count and (pixel, sample, tagged tile pixel).  Integer sums: the image is the legacy loop's.
+// Ring layout, word-major (entry i of array k at [k * 64 + i]: a wave's lanes touch consecutive
+// words): od = origin.xyz, direction.xyz; meta = time word, pixel, sample, tagged tile pixel.
+RT_FN int wave_prefix(unsigned long long m) {  // set bits of m below this lane
+  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+template <class Work>
+RT_FN void lane_loop_flat_ring(const KernelParams& P0, Work& work, real* ring_od, uint32_t* ring_meta) {
+  constexpr int kN = RT_RING_LANES;
+  int cnt = 0;           // entries [0, cnt) of the ring hold rays not yet started (wave-uniform)
+  bool drained = false;  // a refill met the end of the queues: nothing is left to claim (wave-uniform)
+  bool alive = false;
+  uint32_t pix = 0u;
+  int sample = 0, tpk = 0, seg = 0;
+  f3 T = mk3(RL(1.), RL(1.), RL(1.));
+  real apdf = RL(1.);
+  RayCtx R;
+  R.o = R.d = mk3(RL(0.), RL(0.), RL(0.));
+#if RT_NODE_F32
+  R.idir = R.off0 = R.off1 = f3n{0.f, 0.f, 0.f};
+#else
+  R.idir = R.oidir = R.o;
+#endif
+  R.time_w = 0u;
+  R.self_gid = -1;
+  R.self_inst = -1;
+  RT_PROF_DECL
+  for (;;) {
+    const KernelParams& P = RT_KARGS(P0);  // (per iteration: RT_KARGS)
+    const bool need = !alive;
+    const unsigned long long m = __ballot(need);
+    RT_PROF_ADD(PF_ITERS, 1);
+    RT_PROF_ADD(PF_CAM_LANES, (int)__popcll(m));
+    if (m != 0ull) {  // wave-uniform
+      const int rank = wave_prefix(m);
+      int want = (int)__popcll(m), base = 0;  // ranks [base, base + want) are not served yet
+      for (;;) {
+        const int take = want < cnt ? want : cnt;
+        const int k = rank - base;
+        if (need && k >= 0 && k < take) {
+          const int e = cnt - 1 - k;
+          R.o = mk3(ring_od[e], ring_od[kN + e], ring_od[2 * kN + e]);
+          R.d = mk3(ring_od[3 * kN + e], ring_od[4 * kN + e], ring_od[5 * kN + e]);
+          R.time_w = ring_meta[e];
+          pix = ring_meta[kN + e];
+          sample = (int)ring_meta[2 * kN + e];
+          tpk = (int)ring_meta[3 * kN + e];
+          R.self_gid = -1;
+          T = mk3(RL(1.), RL(1.), RL(1.));
+          seg = 0;
+          alive = true;
+        }
+        cnt -= take;
+        base += take;
+        want -= take;
+        if (want == 0 || drained) break;
+        // the ring is empty and lanes still wait: the next 64 samples of the wave's stream, every
+        // lane of the wave active (lanes leave the loop only once `drained`)
+        RT_PROF_ADD(PF_FRONT_LANES, kN);
+        int aslot;
+        const int got = work.grab(true, aslot);
+        const bool in = got < P.n_items;
+        ItemCtx J{-1, 0, 0, 0u, 0u};
+        const bool ok = in && open_item<true>(P, got, J);
+        const int jt = work.tag_ring(J.tp, aslot);  // (with the pixel's place in the slot: WaveWork)
+        work.skip_ring(in && !ok, jt);  // an id without a sample (a padding row, max_depth <= 0)
+        const unsigned long long vm = __ballot(ok);
+        if (ok) {
+          RayCtx C;
+          camera_ray_flat(P, J.pix, J.sample, J.pxgy, C);
+          const int e = wave_prefix(vm);
+          ring_od[e] = C.o.x, ring_od[kN + e] = C.o.y, ring_od[2 * kN + e] = C.o.z;
+          ring_od[3 * kN + e] = C.d.x, ring_od[4 * kN + e] = C.d.y, ring_od[5 * kN + e] = C.d.z;
+          ring_meta[e] = C.time_w;
+          ring_meta[kN + e] = J.pix;
+          ring_meta[2 * kN + e] = (uint32_t)J.sample;
+          ring_meta[3 * kN + e] = (uint32_t)jt;
+        }
+        __builtin_amdgcn_wave_barrier();
+        cnt = (int)__popcll(vm);
+        drained = __ballot(in) != ~0ull;
+      }
+    }
+    RT_PROF_MARK(PF_FRONT);
+    if (!alive) break;  // nothing left for this lane: the queues are drained and the ring is empty
+    // ---- closest hit over the surfaces (Ray.hs:178), the redirect pdf deferred to it
+    Closest C = no_hit();
+    closest_flat<true>(P, 0, R, kTmin, C, &apdf);
+    if (P.target_defer) T = (seg == 0 ? RL(1.) : RT_RCP(apdf)) * T;  // wave-uniform branch
+    RT_PROF_MARK(PF_TRAV);
+    f3 L = mk3(RL(0.), RL(0.), RL(0.));
+    if (shade<0, false, false>(P, cf(P.prims), pix, sample, seg, C.t, C.prim, -1, R, L, T, -1, &apdf)) {
+      // the path ended (R, T and apdf are indeterminate until the next pop: shade's invariant): its
+      // sample's words go to the pixel's sums at once
+      Acc a;
+      acc_clear(a);
+      bool bad = false;
+      acc_sample(a, L, bad);
+      work.commit_ring(tpk, a, bad);
+      alive = false;
+    }
+    RT_PROF_MARK(PF_SHADE);
+  }
+  RT_PROF_FLUSH
+}
+#endif
 
 // The segment's media events after its surface query, with the lanes that shade (KernelParams::
 // media_late: every medium's boundary is the surface set or a single leaf, whose records are the
