@@ -47,6 +47,8 @@ module Graphics.Ray.Device
   , raytraceUntilWith, raytraceDenoisedWith, renderUntilOnDevices, renderDenoisedOnDevices
     -- * 8-bit output encoded on the device (writeImage / writeImageSqrt of a render, Ray.hs:248-260)
   , Encoding(..), renderImage8, raytraceToFile
+    -- * Ray queries on a resident scene (rt.h rt_scene_cast)
+  , DeviceScene, withDeviceScene, hitMany, RtRay(..), RtHit(..)
     -- * Geometry (Geometry.hs:5-16)
   , Geometry(Geometry), boundingBox, pureGeometry, transform, moving
   , sphere, planeShape, parallelogram, cuboid, triangle, triangleMesh, constantMedium
@@ -75,7 +77,7 @@ import Control.Monad.State (State, evalState)
 import Data.Bits (shiftR, xor)
 import Data.List (sortOn)
 import Data.Functor.Identity (Identity)
-import Data.Int (Int32)
+import Data.Int (Int32, Int64)
 import qualified Data.Map.Strict as Map
 import Data.Word (Word64, Word8)
 import qualified Data.Massiv.Array as A
@@ -558,6 +560,12 @@ foreign import ccall safe "rt_scene_create"
   c_rt_scene_create :: Ptr RtScene -> Int32 -> Ptr (Ptr ()) -> IO CInt
 foreign import ccall safe "rt_scene_destroy"
   c_rt_scene_destroy :: Ptr () -> IO CInt
+foreign import ccall safe "rt_scene_cast"
+  c_rt_scene_cast :: Ptr () -> Ptr RtExec -> Ptr RtRay -> Ptr RtHit -> Int64 -> Int32 -> IO CInt
+foreign import ccall safe "rt_scene_cast_async"
+  c_rt_scene_cast_async :: Ptr () -> Ptr RtExec -> Ptr RtRay -> Ptr RtHit -> Int64 -> Int32 -> Ptr () -> IO CInt
+foreign import ccall safe "rt_scene_cast_status"
+  c_rt_scene_cast_status :: Ptr () -> Ptr Int32 -> IO CInt
 foreign import ccall safe "rt_film_create"
   c_rt_film_create :: Ptr () -> Ptr RtCamera -> Word64 -> Ptr RtExec -> Ptr (Ptr ()) -> IO CInt
 foreign import ccall safe "rt_film_destroy"
@@ -628,6 +636,22 @@ foreign import ccall safe "rt_multi_film_frame"
 -- LAYOUT rt_camera_settings.defocus_angle 152
 -- LAYOUT rt_camera_settings.n_redirect_targets 168
 -- LAYOUT rt_camera_settings.redirect_targets 176
+-- LAYOUT rt_ray 80
+-- LAYOUT rt_ray.origin 0
+-- LAYOUT rt_ray.dir 24
+-- LAYOUT rt_ray.tmin 48
+-- LAYOUT rt_ray.tmax 56
+-- LAYOUT rt_ray.time 64
+-- LAYOUT rt_hit 96
+-- LAYOUT rt_hit.t 0
+-- LAYOUT rt_hit.point 8
+-- LAYOUT rt_hit.normal 32
+-- LAYOUT rt_hit.uv 56
+-- LAYOUT rt_hit.hit 72
+-- LAYOUT rt_hit.front 76
+-- LAYOUT rt_hit.leaf 80
+-- LAYOUT rt_hit.instance 84
+-- LAYOUT rt_hit.material 88
 -- LAYOUT rt_exec 32
 -- LAYOUT rt_exec.flags 16
 -- LAYOUT rt_exec.n_devices 20
@@ -960,6 +984,86 @@ raytraceWith opts settings world gen =
 -- | A failing library call as a 'RenderError' (the thread's rt_last_error message).
 libraryError :: CInt -> IO (Either RenderError a)
 libraryError rc = Left . LibraryError (fromIntegral rc) <$> (c_rt_last_error >>= peekCString)
+
+-- ---------------------------------------------------------------- ray queries (rt.h rt_scene_cast)
+
+-- | rt_ray (80 bytes): origin, direction (any non-zero length; the library normalises it, so the
+-- hit's t is a distance — the reference's hr_t for a unit direction), the open interval and the time.
+data RtRay = RtRay { rayOrigin :: !Vec3, rayDir :: !Vec3, rayTmin :: !Double, rayTmax :: !Double, rayTime :: !Double }
+
+-- | rt_hit (96 bytes).  hitFlag: 1 hit, 0 miss, -1 malformed ray.
+data RtHit = RtHit { hitT :: !Double, hitPoint :: !Vec3, hitNormal :: !Vec3, hitUV :: !(V2 Double), hitFlag :: !Int32
+                   , hitFront :: !Int32, hitLeaf :: !Int32, hitInstance :: !Int32, hitMaterial :: !Int32 }
+
+peekD :: Ptr a -> Int -> IO Double
+peekD p off = realToFrac <$> (peekByteOff p off :: IO CDouble)
+
+peekV3 :: Ptr a -> Int -> IO Vec3
+peekV3 p off = V3 <$> peekD p off <*> peekD p (off + 8) <*> peekD p (off + 16)
+
+instance Storable RtRay where
+  sizeOf _ = 80
+  alignment _ = 8
+  peek p = RtRay <$> peekV3 p 0 <*> peekV3 p 24 <*> peekD p 48 <*> peekD p 56 <*> peekD p 64
+  poke p (RtRay (V3 ox oy oz) (V3 dx dy dz) tmin tmax time) =
+    pokeDoubles p 0 [ox, oy, oz] >> pokeDoubles p 24 [dx, dy, dz] >> pokeDoubles p 48 [tmin, tmax, time, 0]
+
+instance Storable RtHit where
+  sizeOf _ = 96
+  alignment _ = 8
+  peek p = RtHit <$> peekD p 0 <*> peekV3 p 8 <*> peekV3 p 32 <*> (V2 <$> peekD p 56 <*> peekD p 64)
+                 <*> peekByteOff p 72 <*> peekByteOff p 76 <*> peekByteOff p 80 <*> peekByteOff p 84 <*> peekByteOff p 88
+  poke p (RtHit t (V3 px py pz) (V3 nx ny nz) (V2 u v) flag front leaf inst mat) = do
+    pokeDoubles p 0 [t, px, py, pz, nx, ny, nz, u, v]
+    zipWithM_ (\k x -> pokeI32 p (72 + 4 * k) x) [0 ..] [flag, front, leaf, inst, mat, 0]
+
+-- | A scene resident on one GPU (rt_scene_create), for 'hitMany'.
+newtype DeviceScene = DeviceScene (Ptr ())
+
+-- | Flatten and upload @world@ to device @dev@, run the continuation, release the scene.
+-- 'NotReifiable' for a world the device cannot evaluate (custom closures).
+withDeviceScene :: Int -> Geometry m Material -> (DeviceScene -> IO a) -> IO (Either RenderError a)
+withDeviceScene dev world k =
+  case geoDesc world of
+    Nothing -> pure (Left NotReifiable)
+    Just desc -> do
+      tagged <- tagShared desc
+      case flatten tagged of
+        Nothing -> pure (Left NotReifiable)
+        Just flat ->
+          withFlatScene flat $ \sc -> alloca $ \pscene -> do
+            rc <- c_rt_scene_create sc (fromIntegral dev) pscene
+            if rc /= 0 then libraryError rc else do
+              scene <- peek pscene
+              r <- k (DeviceScene scene)
+              _ <- c_rt_scene_destroy scene
+              pure (Right r)
+
+-- | The reference's @Geometry@ hit function (Geometry.hs:42) for many rays at once, in binary64:
+-- for each @(time, ray, (tmin, tmax))@ the closest surface hit in the open interval and the index
+-- of its material in the flattened scene's material table (the placement's material for an
+-- instanced leaf that has one), or Nothing for a miss or a malformed ray.  Volumes
+-- ('constantMedium') are not hit.  The ray's direction need not be unit; hr_t is a distance along
+-- it, the reference's hr_t when it is unit.  A failing call (RT_E_STACK included) is an 'IOError'.
+hitMany :: DeviceScene -> [(Double, Ray, Interval)] -> IO [Maybe (HitRecord, Int)]
+hitMany _ [] = pure []
+hitMany (DeviceScene scene) queries =
+  let n = length queries
+      rays = [ RtRay o d tmin tmax time | (time, Ray o d, (tmin, tmax)) <- queries ]
+  in withArray rays $ \prays -> allocaArray n $ \phits -> allocaBytes 32 $ \ex -> do
+       fillBytes ex 0 32
+       pokeI32 ex 4 (1 :: Int32)    -- n_shards
+       pokeI32 ex 12 (4 :: Int32)   -- row_block; flags 0: binary64
+       rc <- c_rt_scene_cast scene (castPtr ex) prays phits (fromIntegral n) 1   -- RT_QUERY_UV
+       if rc /= 0
+         then c_rt_last_error >>= peekCString >>= \msg -> ioError (userError ("rt_scene_cast: " ++ msg))
+         else map toRecord <$> peekArray n phits
+  where
+    toRecord h
+      | hitFlag h /= 1 = Nothing
+      | otherwise = Just ( HitRecord { hr_t = hitT h, hr_point = hitPoint h, hr_normal = hitNormal h
+                                     , hr_frontSide = hitFront h /= 0, hr_uv = hitUV h }
+                         , fromIntegral (hitMaterial h) )
 
 -- | Render progressively on one GPU through a film (rt.h rt_film_*): passes of @batch@ samples
 -- until the frame's noise figure (rt_film_noise, checked from the second pass on) is at most

@@ -466,6 +466,74 @@ int rt_denoise_albedo_read(const rt_film* f, int64_t* host_words, int32_t* n_alb
 int rt_denoise_film(rt_film* f, const rt_denoise_params* p, void* d_out_rgb, void* hip_stream);
 int rt_denoise_film_read(rt_film* f, const rt_denoise_params* p, void* host_out_rgb);
 
+/* Batched ray queries on a resident scene: closest hit and any hit.
+ *
+ * The reference's other public type is `Geometry`: a hit function time -> Ray -> (tmin, tmax) ->
+ * Maybe (HitRecord, a) (Geometry.hs:42, Core.hs:155-160).  rt_scene_cast evaluates it for n rays
+ * against the scene's SURFACE set, exactly as segment 0 of a render queries it (the flat sets, or the
+ * surface prefix and the BVH traversal of the scene's kernel class).  `constantMedium` volumes are
+ * not hit: their events are random draws keyed by pixel and sample, which a query does not have.
+ *
+ * rt_ray: the ray origin + t dir / |dir|.  The direction may have any non-zero length and is
+ *   normalised in binary64 before anything else, so t is a DISTANCE; the reference's sphere test
+ *   assumes a unit direction (Geometry.hs:63-68), so for unit directions t is its hr_t.  The interval
+ *   (tmin, tmax) is open at both ends, 0 <= tmin < tmax, tmax may be +infinity (with RT_EXEC_F32 both
+ *   ends are rounded to float first).  time in [0, 1] places `moving` geometry; the kernel keeps it as
+ *   the render does, in 24 bits: floor(time 2^24) / 2^24, and a time of 1 is 1 - 2^-24.
+ * rt_hit: hit = 1 with every field set, 0 for a miss, -1 for a malformed ray (a non-finite field,
+ *   a zero direction, tmin < 0, tmax <= tmin, time outside [0, 1]): nothing else in the record is
+ *   defined then.  normal is the unit normal facing the ray, as the materials see it (hr_normal), and
+ *   front is hr_frontSide; for an instanced leaf the point is the world-space one and the normal is
+ *   rotated to world space.  leaf is the leaf's depth-first order in the caller's tree (rt_prim.order;
+ *   an instanced object's leaf: rt_instance.order + its order inside the object; a flat scene
+ *   reports the leaf's rank among the surface leaves in that order) — on equal t the smaller one
+ *   wins, as in the reference (Geometry.hs:340-361).  instance is the rt_scene.instances index of the
+ *   placement or -1; material the rt_scene.materials index, the placement's material where it has one.
+ * flags: RT_QUERY_UV computes uv (sphereUV or the plane shape's uv lerp), without it uv is 0.
+ *   RT_QUERY_ANY_HIT asks only WHETHER the interval holds a hit: hit is exactly the closest-hit
+ *   query's, t is the distance of some accepted hit inside the interval, every other field is
+ *   unspecified; the BVH classes leave their traversal at the first accepted hit.
+ * Rays are neither sorted nor compacted: one lane per ray, 64 consecutive rays per wave, so the
+ *   caller's ray order is the kernel's coherence.
+ *
+ * rt_scene_cast_async: d_rays / d_hits are device buffers of n records on the scene's device;
+ *   enqueues on hip_stream.  ex gives the precision (RT_EXEC_F32) and must name no device list; the
+ *   first cast of a precision uploads that precision's records (as a first render does) and is not
+ *   asynchronous.  n == 0 is a no-op.  A traversal-stack overflow sets a word of the scene that stays
+ *   set until rt_scene_cast_status reads it.
+ * rt_scene_cast: the same from and to host buffers, synchronous; RT_E_STACK (hits written) if a
+ *   traversal stack overflowed.
+ * rt_scene_cast_status: *overflowed = 1 if an rt_scene_cast_async since the last call overflowed a
+ *   traversal stack (such rays' records are not reliable), and clears the word; call it after
+ *   synchronising the casts' stream.
+ * Null arguments and n < 0 are RT_E_INVALID before any device call. */
+#define RT_QUERY_UV 1
+#define RT_QUERY_ANY_HIT 2
+typedef struct rt_ray {
+  double origin[3];
+  double dir[3];
+  double tmin, tmax;
+  double time;
+  double reserved;   /* not read: the record is 80 bytes, five 16-byte vectors */
+} rt_ray;
+typedef struct rt_hit {
+  double t;
+  double point[3];
+  double normal[3];
+  double uv[2];
+  int32_t hit;       /* 1 hit, 0 miss, -1 malformed ray */
+  int32_t front;     /* hr_frontSide */
+  int32_t leaf;
+  int32_t instance;  /* or -1 */
+  int32_t material;
+  int32_t reserved;
+} rt_hit;
+int rt_scene_cast_async(const rt_device_scene* s, const rt_exec* ex, const rt_ray* d_rays, rt_hit* d_hits, int64_t n,
+                        int32_t flags, void* hip_stream);
+int rt_scene_cast(const rt_device_scene* s, const rt_exec* ex, const rt_ray* host_rays, rt_hit* host_hits, int64_t n,
+                  int32_t flags);
+int rt_scene_cast_status(const rt_device_scene* s, int32_t* overflowed);
+
 #ifdef __cplusplus
 }
 #endif

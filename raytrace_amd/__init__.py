@@ -18,6 +18,7 @@ from .geometry import (M44, Mesh, ObjParseError, boundingBox, bvhNode, bvhTree, 
 from .material import (Material, Texture, anisotropic, checkerTexture, constantTexture, dielectric, imageTexture,
                        isotropic, lambertian, lightSource, lommelSeeliger, marbleTexture, metal, mirror, noiseTexture,
                        pitchBlack, solidTexture, transparent, uvTexture)
+from .query import HIT_DTYPE, RAY_DTYPE, cast, hits_dict, make_rays
 from .ray import DeviceScene, MultiDeviceScene, encode8, raytrace, readImage, render_shard, writeImage, writeImageSqrt
 from .scene import FlatScene, flatten
 

@@ -25,7 +25,8 @@ EXPORTED = ["rt_abi_version", "rt_last_error", "rt_device_count", "rt_image_heig
             "rt_multi_film_create", "rt_multi_film_destroy", "rt_multi_film_reset", "rt_multi_film_add",
             "rt_multi_film_load", "rt_multi_film_frame", "rt_multi_film_copies",
             "rt_denoise_default_params", "rt_denoise_features", "rt_denoise_albedo", "rt_denoise_features_read", "rt_denoise_albedo_read", "rt_denoise_film",
-            "rt_denoise_film_read"]
+            "rt_denoise_film_read",
+            "rt_scene_cast_async", "rt_scene_cast", "rt_scene_cast_status"]
 
 
 class RtRedirectTarget(ctypes.Structure):
@@ -64,6 +65,8 @@ RT_EXEC_F32 = 1  # rt_exec.flags: FP32 kernel, float output (default: binary64, 
 RT_EXEC_ENCODE8_SRGB = 2  # rt_render output: uint8 codes of writeImage (sRGB)
 RT_EXEC_ENCODE8_SQRT = 4  # rt_render output: uint8 codes of writeImageSqrt
 RT_EXEC_SOLO = 8  # rt_render_async: the render runs alone (planned for a short end, as rt_render's)
+RT_QUERY_UV = 1  # rt_scene_cast flags: compute uv
+RT_QUERY_ANY_HIT = 2  # ... an occlusion query: only `hit` and some accepted `t`
 ENCODINGS = {None: 0, "srgb": RT_EXEC_ENCODE8_SRGB, "sqrt": RT_EXEC_ENCODE8_SQRT}
 ABI_VERSION = 6
 PRECISIONS = {"f64": np.float64, "f32": np.float32}
@@ -84,6 +87,17 @@ class RtStats(ctypes.Structure):
 class RtFilmInfo(ctypes.Structure):
     _fields_ = [("samples", ctypes.c_int64), ("passes", ctypes.c_int32), ("width", ctypes.c_int32),
                 ("rows", ctypes.c_int32), ("nan_pixels", ctypes.c_int32), ("f32", ctypes.c_int32)]
+
+
+class RtRay(ctypes.Structure):
+    _fields_ = [("origin", ctypes.c_double * 3), ("dir", ctypes.c_double * 3), ("tmin", ctypes.c_double),
+                ("tmax", ctypes.c_double), ("time", ctypes.c_double), ("reserved", ctypes.c_double)]
+
+
+class RtHit(ctypes.Structure):
+    _fields_ = [("t", ctypes.c_double), ("point", ctypes.c_double * 3), ("normal", ctypes.c_double * 3),
+                ("uv", ctypes.c_double * 2), ("hit", ctypes.c_int32), ("front", ctypes.c_int32), ("leaf", ctypes.c_int32),
+                ("instance", ctypes.c_int32), ("material", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class RtDenoiseParams(ctypes.Structure):
@@ -152,6 +166,9 @@ def load():
     L.rt_denoise_albedo_read.argtypes = [P, P, ctypes.POINTER(ctypes.c_int32)]
     L.rt_denoise_film.argtypes = [P, ctypes.POINTER(RtDenoiseParams), P, P]
     L.rt_denoise_film_read.argtypes = [P, ctypes.POINTER(RtDenoiseParams), P]
+    L.rt_scene_cast_async.argtypes = [P, ctypes.POINTER(RtExec), P, P, ctypes.c_int64, ctypes.c_int32, P]
+    L.rt_scene_cast.argtypes = [P, ctypes.POINTER(RtExec), P, P, ctypes.c_int64, ctypes.c_int32]
+    L.rt_scene_cast_status.argtypes = [P, ctypes.POINTER(ctypes.c_int32)]
     for name in EXPORTED:
         getattr(L, name)
     if L.rt_abi_version() != ABI_VERSION:

@@ -112,7 +112,8 @@ struct rt_device_scene {
   int device = 0;
   float* nodes = nullptr;
   int* perlin_perm = nullptr;
-  int* status = nullptr;
+  int* status = nullptr;     // 4 words: [0] the renders' stack overflow, [1] / [2] the asynchronous / synchronous casts'
+  mutable int* prim_mat = nullptr;  // HostScene::prim_mat, uploaded by the first cast (rt_scene_cast*)
   // a precision's records are uploaded (and its kernel's occupancy queried) on its first render:
   // a caller that renders one precision never pays for the other's copy in HBM or its upload
   std::shared_ptr<const HostScene> host;
@@ -405,6 +406,7 @@ void destroy_scene(rt_device_scene* s) {
   (void)hipFree(s->nodes);
   (void)hipFree(s->perlin_perm);
   (void)hipFree(s->status);
+  (void)hipFree(s->prim_mat);
   s->f32.release();
   s->f64.release();
   delete s;
@@ -873,6 +875,62 @@ int film_features(rt_film* f, unsigned long long* feat, int n_feat, hipStream_t 
   if (rt_launch_features(P, s->variant, feat, n_feat, st))
     return fail(RT_E_HIP, "feature launch failed: %s", hipGetErrorString(hipGetLastError()));
   return RT_OK;
+}
+
+// ---- ray queries (include/rt.h rt_scene_cast; rt_query.h)
+
+// n queries of precision R enqueued on st; a stack overflow sets the scene's status word `word`
+template <class R>
+int cast_enqueue(const rt_device_scene* s, const rt_ray* d_rays, rt_hit* d_hits, int64_t n, int flags, int word,
+                 hipStream_t st) {
+  if (int rc = ensure_precision<R>(s)) return rc;
+  {
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (!s->prim_mat) {
+      HIP_TRY(hipSetDevice(s->device));
+      int* d = nullptr;
+      if (int rc = upload(&d, s->host->prim_mat)) return rc;
+      s->prim_mat = d;
+    }
+  }
+  // the scene parts of a render's argument block are what the kernel reads: a valid 1 x 1 camera fills the rest
+  rt_camera_settings cs{};
+  cs.look_at[2] = -1.0;
+  cs.up[1] = 1.0;
+  cs.vfov = 1.0;
+  cs.aspect_ratio = 1.0;
+  cs.image_width = cs.samples_per_pixel = cs.max_recursion_depth = 1;
+  cs.focus_dist = 1.0;
+  rt_exec ex{};
+  ex.device = s->device;
+  ex.n_shards = 1;
+  ex.row_block = 4;
+  LaunchInputs L;
+  L.resident_lanes = 4096;  // (the work plan is the render's; the query kernel has none)
+  L.lds_nodes = 0;          // no staged nodes: every node from memory
+  KernelParamsT<R> P;
+  std::string err;
+  if (int rc = rt_host_render_params(*s->host, s->variant, s->arrays<R>().rec, &cs, 0, &ex, L, P, err))
+    return fail(rc, "%s", err.c_str());
+  P.status = s->status + word;
+  // (experiments and tests: fewer stack rows than the scene's BVH needs, the defined overflow path)
+  if (const char* e = rt_knob("RT_AMD_CAST_STACK")) P.stack_depth = std::max(1, std::min(P.stack_depth, atoi(e)));
+  HIP_TRY(hipSetDevice(s->device));
+  if (rt_launch_query(P, s->variant, d_rays, d_hits, s->prim_mat, (long long)n, flags, st))
+    return fail(RT_E_HIP, "query launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return RT_OK;
+}
+
+// the checks of a cast that need no device
+int cast_check(const rt_device_scene* s, const rt_exec* ex, const rt_ray* rays, const rt_hit* hits, int64_t n, int flags) {
+  if (!s) return fail(RT_E_INVALID, "null scene");
+  if (!ex) return fail(RT_E_INVALID, "null rt_exec");
+  if (!rays) return fail(RT_E_INVALID, "null ray buffer");
+  if (!hits) return fail(RT_E_INVALID, "null hit buffer");
+  if (n < 0) return fail(RT_E_INVALID, "negative ray count %lld", (long long)n);
+  if (flags & ~(RT_QUERY_UV | RT_QUERY_ANY_HIT)) return fail(RT_E_INVALID, "unknown query flags 0x%x", flags);
+  if (ex->n_devices != 0) return fail(RT_E_INVALID, "a cast runs on the scene's device (n_devices = 0)");
+  return check_flags(ex);
 }
 
 // the checks of rt_denoise_film / _read that need no device; p: the parameters in effect
@@ -1586,6 +1644,50 @@ int rt_denoise_film_read(rt_film* f, const rt_denoise_params* p, void* host_out_
   if (int rc = film_denoise(f, &dp, f->tile, f->last)) return rc;
   HIP_TRY(hipMemcpyAsync(host_out_rgb, f->tile, f->n_pixels * 3 * elem_size_of(f->f32), hipMemcpyDeviceToHost, f->last));
   HIP_TRY(hipStreamSynchronize(f->last));
+  return RT_OK;
+}
+
+int rt_scene_cast_async(const rt_device_scene* s, const rt_exec* ex, const rt_ray* d_rays, rt_hit* d_hits, int64_t n,
+                        int32_t flags, void* hip_stream) {
+  if (int rc = cast_check(s, ex, d_rays, d_hits, n, flags)) return rc;
+  if (n == 0) return RT_OK;
+  return exec_f32(ex) ? cast_enqueue<float>(s, d_rays, d_hits, n, flags, 1, (hipStream_t)hip_stream)
+                      : cast_enqueue<double>(s, d_rays, d_hits, n, flags, 1, (hipStream_t)hip_stream);
+}
+
+int rt_scene_cast(const rt_device_scene* s, const rt_exec* ex, const rt_ray* host_rays, rt_hit* host_hits, int64_t n,
+                  int32_t flags) {
+  if (int rc = cast_check(s, ex, host_rays, host_hits, n, flags)) return rc;
+  if (n == 0) return RT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  char* mem = nullptr;
+  const size_t ray_bytes = (size_t)n * sizeof(rt_ray), hit_bytes = (size_t)n * sizeof(rt_hit);
+  HIP_TRY(hipMalloc((void**)&mem, ray_bytes + hit_bytes));  // (both multiples of 16 bytes)
+  rt_ray* d_rays = (rt_ray*)mem;
+  rt_hit* d_hits = (rt_hit*)(mem + ray_bytes);
+  int status = 0;
+  int rc = RT_OK;
+  if (hipMemcpy(d_rays, host_rays, ray_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(s->status + 2, 0, sizeof(int)) != hipSuccess)
+    rc = fail(RT_E_HIP, "ray upload failed: %s", hipGetErrorString(hipGetLastError()));
+  if (!rc)
+    rc = exec_f32(ex) ? cast_enqueue<float>(s, d_rays, d_hits, n, flags, 2, nullptr)
+                      : cast_enqueue<double>(s, d_rays, d_hits, n, flags, 2, nullptr);
+  if (!rc && (hipMemcpy(host_hits, d_hits, hit_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+              hipMemcpy(&status, s->status + 2, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess))
+    rc = fail(RT_E_HIP, "hit read-back failed: %s", hipGetErrorString(hipGetLastError()));
+  (void)hipFree(mem);
+  if (!rc && status) return fail(RT_E_STACK, "BVH traversal stack overflow");
+  return rc;
+}
+
+int rt_scene_cast_status(const rt_device_scene* s, int32_t* overflowed) {
+  if (!s || !overflowed) return fail(RT_E_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  int status = 0;
+  HIP_TRY(hipMemcpy(&status, s->status + 1, sizeof(int), hipMemcpyDeviceToHost));
+  if (status) HIP_TRY(hipMemset(s->status + 1, 0, sizeof(int)));
+  *overflowed = status ? 1 : 0;
   return RT_OK;
 }
 

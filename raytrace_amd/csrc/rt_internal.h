@@ -524,6 +524,15 @@ int rt_launch_resolve(const KernelParams64& p, void* stream);
 // (rt_host_render_params) with lds_nodes = 0 and status set
 int rt_launch_features(const KernelParams& p, int variant, unsigned long long* feat, int n_feat, void* stream);
 int rt_launch_features(const KernelParams64& p, int variant, unsigned long long* feat, int n_feat, void* stream);
+// rt_query.hip / rt_query64.hip (+ rt_query64_bvh.hip): n ray queries (include/rt.h rt_scene_cast; rt_query.h), device
+// pointers.  p as a render's (rt_host_render_params, any valid camera) with lds_nodes = 0 and status
+// set; prim_mat: HostScene::prim_mat on the device
+struct rt_ray;
+struct rt_hit;
+int rt_launch_query(const KernelParams& p, int variant, const rt_ray* rays, rt_hit* hits, const int* prim_mat, long long n,
+                    int flags, void* stream);
+int rt_launch_query(const KernelParams64& p, int variant, const rt_ray* rays, rt_hit* hits, const int* prim_mat,
+                    long long n, int flags, void* stream);
 #if defined(RT_PHASE_PROF)
 int rt_prof_read_kernel(const KernelParams*, unsigned long long* out, int n);
 int rt_prof_read_kernel(const KernelParams64*, unsigned long long* out, int n);

@@ -1,0 +1,136 @@
+// rt_query.h — one ray query of ONE precision (include/rt.h rt_scene_cast): included after rt_trace.h
+// of the same RT_F64 (no include guard, as rt_trace.h's per-precision part), by rt_query.hip /
+// rt_query64.hip / rt_query64_nl.hip for the device and by tests/query_emu for the host (RT_HOST_EMU).
+//
+// query_ray turns one rt_ray into one rt_hit against the scene's surface set, as segment 0 of a
+// render queries it (rt_features.h feature_sample's `query`): the flat sets through closest<true>,
+// otherwise the surface prefix and trav_round with the class's instancing and leaf flags.  What
+// differs from a camera ray: the ray is the caller's (normalised in binary64 before it is converted
+// to the kernel's precision), its time word is floor(time 2^24) << 8 (u01 of it is the time the
+// kernel sees, rt_trace.h u01), tmin stands where kTmin does, and tmax enters as the initial Closest
+// ({tmax, 0, -1, -1}; FP32: the key hit_key(tmax, 0)), so a candidate needs t < tmax strictly — no
+// leaf's key order is below 0.  self_gid / self_inst are -1: a query ray leaves no leaf.  Media are
+// not queried (their events are random draws keyed by pixel and sample).
+#include "../../include/rt.h"
+
+namespace RT_NS {
+
+// a ray the kernel can trace: finite fields, a direction that is not zero, 0 <= tmin < tmax, time in [0, 1]
+RT_FN bool query_ray_ok(const rt_ray& q) {
+  const double s = q.origin[0] + q.origin[1] + q.origin[2] + q.dir[0] + q.dir[1] + q.dir[2] + q.tmin + q.time;
+  const bool finite = fabs(s) < __builtin_huge_val() && fabs(q.origin[0]) < __builtin_huge_val() &&
+                      fabs(q.origin[1]) < __builtin_huge_val() && fabs(q.origin[2]) < __builtin_huge_val() &&
+                      fabs(q.dir[0]) < __builtin_huge_val() && fabs(q.dir[1]) < __builtin_huge_val() &&
+                      fabs(q.dir[2]) < __builtin_huge_val();
+  const bool dir = q.dir[0] != 0.0 || q.dir[1] != 0.0 || q.dir[2] != 0.0;
+  return finite && dir && q.tmin >= 0.0 && q.tmax > q.tmin && q.time >= 0.0 && q.time <= 1.0;  // (a NaN tmax fails)
+}
+
+// kVar, kInst, kLeaf: the scene's kernel class (rt_kernel_class.h), the fields a surface hit sees.
+// prim_mat: the material index of every primitive (rt_internal.h HostScene::prim_mat).
+template <int kVar, bool kInst, int kLeaf>
+RT_FN void query_ray(const KernelParams& P0, const real* prims_, const int* prim_mat, const Trav& W, const rt_ray& q,
+                     int flags, rt_hit& H, int& overflow) {
+  constexpr bool kFlat = kVar == RT_VAR_FLAT;
+  H = rt_hit{};
+  H.instance = -1;
+  H.material = -1;
+  H.leaf = -1;
+  if (!query_ray_ok(q)) {
+    H.hit = -1;
+    return;
+  }
+  const cfp prims = cf(prims_);
+  const bool any = (flags & RT_QUERY_ANY_HIT) != 0;
+  // dir / |dir| in binary64, scaled by its largest component first (no overflow or underflow of the squares)
+  const double m = fmax(fmax(fabs(q.dir[0]), fabs(q.dir[1])), fabs(q.dir[2]));
+  const double dx = q.dir[0] / m, dy = q.dir[1] / m, dz = q.dir[2] / m;
+  const double il = 1.0 / sqrt(dx * dx + dy * dy + dz * dz);
+  RayCtx R;
+  R.o = mk3((real)q.origin[0], (real)q.origin[1], (real)q.origin[2]);
+  R.d = mk3((real)(dx * il), (real)(dy * il), (real)(dz * il));
+#if RT_NODE_F32
+  R.idir = R.off0 = R.off1 = f3n{0.f, 0.f, 0.f};
+#else
+  R.idir = R.oidir = mk3(RL(0.), RL(0.), RL(0.));
+#endif
+  const double tw = floor(q.time * 16777216.0);
+  R.time_w = (uint32_t)(tw > 16777215.0 ? 16777215.0 : tw) << 8;
+  R.self_gid = -1;
+  R.self_inst = -1;
+  const real tmin = (real)q.tmin, tmax = (real)q.tmax;
+  Closest C = no_hit();
+  C.t = tmax;
+#if !RT_F64
+  const unsigned long long key0 = hit_key(tmax, 0);
+  C.key = key0;
+#endif
+  bool hit;
+  {
+    // (the kernel arguments re-read, as the render's lane loops do: rt_trace.h RT_KARGS)
+    const KernelParams& P = RT_KARGS(P0);
+    if constexpr (kFlat) {
+      closest<true>(P, prims, P.surface_root, 0, R, tmin, C, W, &overflow);
+#if RT_F64
+      hit = C.t < tmax;  // every accepted candidate is below tmax
+      C.prim = C.ord;    // slot = primitive index (rt_trace.h closest_flat)
+#else
+      hit = C.key < key0;
+#endif
+    } else {
+      prep_ray(R);
+      TravState S;
+      trav_begin(S, P.surface_root, tmin);
+      S.C = C;
+      prefix_hits<kInst>(P, prims, R, tmin, S.C);
+      // any-hit: the traversal ends at the first accepted hit
+      while (!trav_done(S) && !(any && S.C.prim >= 0)) trav_round<kInst, kLeaf>(P, R, S, W, overflow RT_PROF_NULLARG);
+      C = S.C;
+      hit = C.prim >= 0;
+    }
+  }
+  if (!hit) {
+    H.t = __builtin_huge_val();
+    return;
+  }
+  H.hit = 1;
+  H.t = (double)C.t;
+  if (any) return;
+  const KernelParams& P = RT_KARGS(P0);
+  const int best = C.prim, best_inst = kInst ? C.inst : -1;
+#if RT_F64
+  H.leaf = C.ord;
+#else
+  H.leaf = (int)(uint32_t)C.key;
+#endif
+  H.instance = best_inst;
+  int mat = ldci(prim_mat, best);
+  const bool need_uv = (flags & RT_QUERY_UV) != 0;
+  HitInfo h;
+  bool in_object = false;
+  if constexpr (kInst) {
+    if (best_inst >= 0) {  // hit information in object space, point and normal back to world (rt_features.h)
+      const RT_CAS DevInstance* I = inst_rec(P, best_inst);
+      const int im = I->material;
+      if (im >= 0) mat = im;
+      RayCtx Ro = R;
+      Ro.o = inst_to_object(I, R.o, true);
+      Ro.d = inst_to_object(I, R.d, false);
+      h = surface_info(P, prims, best, Ro, C.t, need_uv);
+      h.p = R.o + C.t * R.d;
+      h.n = inst_rotate(I, h.n);
+      in_object = true;
+    }
+  }
+  if (!in_object) h = surface_info(P, prims, best, R, C.t, need_uv);
+  // a sphere's (p - c) / r is unit up to the hit point's rounding over r (eps |p| / r, many eps for
+  // a small sphere far from the origin): the record's normal is re-normalised
+  h.n = unit(h.n);
+  H.material = mat;
+  H.front = h.front ? 1 : 0;
+  H.point[0] = (double)h.p.x, H.point[1] = (double)h.p.y, H.point[2] = (double)h.p.z;
+  H.normal[0] = (double)h.n.x, H.normal[1] = (double)h.n.y, H.normal[2] = (double)h.n.z;
+  H.uv[0] = (double)h.u, H.uv[1] = (double)h.v;
+}
+
+}  // namespace RT_NS

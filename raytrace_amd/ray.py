@@ -147,6 +147,38 @@ class DeviceScene:
         _lib.check(self._lib.rt_render_async(self.handle, ctypes.byref(cs), _seed64(seed), ctypes.byref(ex),
                                              ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream_ptr or None)))
 
+    @property
+    def materials(self):
+        """The scene description's Material objects, indexed by a cast's `material`."""
+        return self.flat.material_objects
+
+    def cast(self, origins, directions, tmin=1e-4, tmax=np.inf, time=0.0, precision: str = "f64",
+             any_hit: bool = False, uv: bool = True) -> dict:
+        """Closest hit (or, with any_hit, whether there is one) of n rays against the scene's surfaces
+        (rt_scene_cast; raytrace_amd.query).  The arguments broadcast to (n, 3) / (n,); directions
+        need not be unit, t is a distance.  Returns numpy arrays: hit (bool), valid, t (inf on a miss),
+        point, normal, front, uv, leaf, instance, material (an index into `materials`)."""
+        from . import query
+        return query.hits_dict(query.cast_records(self, query.make_rays(origins, directions, tmin, tmax, time),
+                                                  precision, any_hit, uv))
+
+    def cast_async(self, rays_ptr: int, hits_ptr: int, n: int, stream_ptr: int = 0, precision: str = "f64",
+                   any_hit: bool = False, uv: bool = True):
+        """Enqueue n queries from the device buffer of rt_ray records at rays_ptr (query.RAY_DTYPE) into
+        the rt_hit records at hits_ptr (query.HIT_DTYPE), e.g. torch uint8 tensors' data_ptr()."""
+        from . import query
+        ex = _lib.exec_struct(device=self.device, precision=precision)
+        _lib.check(self._lib.rt_scene_cast_async(self.handle, ctypes.byref(ex), ctypes.c_void_p(rays_ptr),
+                                                 ctypes.c_void_p(hits_ptr), int(n), query.query_flags(any_hit, uv),
+                                                 ctypes.c_void_p(stream_ptr or None)))
+
+    def cast_overflowed(self) -> bool:
+        """Whether a cast_async since the last call overflowed a traversal stack (rt_scene_cast_status);
+        call after synchronising the casts' stream."""
+        w = ctypes.c_int32(0)
+        _lib.check(self._lib.rt_scene_cast_status(self.handle, ctypes.byref(w)))
+        return bool(w.value)
+
     def close(self):
         if self.handle:
             self._lib.rt_scene_destroy(self.handle)

@@ -141,6 +141,7 @@ class FlatScene:
         self.motions = motions
         self.uvframes = uvframes
         self.n_surface = n_surface
+        self.material_objects = None  # flatten: the description's Material of every `materials` row
 
     def __repr__(self):
         return (f"FlatScene({len(self.prims)} prims, {len(self.media)} media, {len(self.materials)} materials, "
@@ -338,7 +339,9 @@ def flatten(world: G.Geometry, instance_min: int = INSTANCE_MIN_LEAVES) -> FlatS
         uvf[k]["r"] = r
     n_surface = int(np.sum(prims["set"] == 0)) if len(prims) else 0
     tex, texels, perlin = tabs.texture_array()
-    return FlatScene(prims, med, tabs.material_array(), tex, mot, uvf, n_surface, texels, perlin, inst)
+    flat = FlatScene(prims, med, tabs.material_array(), tex, mot, uvf, n_surface, texels, perlin, inst)
+    flat.material_objects = list(tabs.materials)  # index -> the description's Material (a cast's `material`)
+    return flat
 
 
 M_SPHERE_KIND = PRIM_SPHERE
