@@ -266,8 +266,8 @@ struct WaveWork {
     }
     if (bad) atomicOr(kp().nanflag + tp, 1u);
   }
-  // The ring form (rt_trace.h lane_loop_flat_ring) commits every sample, from the few lanes whose
-  // path has just ended, so the slot's pixel is resolved where the id is opened, by the whole
+  // The ring form (rt_trace.h lane_loop_flat_ring) commits every sample (64 wide at a refill:
+  // flush_ring), so the slot's pixel is resolved where the id is opened, by the whole
   // wave: the code carries the slot + 1 in bits 24-26 and the pixel's offset within the slot in bits
   // 27-31 (tag_ring), and the commit adds the sample's words without reading the header or testing
   // them for zero (one exec region instead of seven)

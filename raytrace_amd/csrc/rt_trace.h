@@ -2070,19 +2070,50 @@ RT_FN int lane_loop_lockstep(const KernelParams& P0, Work& work, const Trav& TW,
 // steal_sample).  A finished sample adds its fixed-point words straight to its pool's aggregation
 // slot (work.commit_ring), so a lane carries no item sums: its state is the ray, T, apdf, the segment
 // count and (pixel, sample, tagged tile pixel).  Integer sums: the image is the legacy loop's.
+// The conversion and the additions run 64 wide, not for the ~19 lanes whose path just ended: such a
+// lane keeps the radiance in T under its tag (-1: no sample held), leaves both in the ring entry it
+// pops next (the freed origin words and tag word), and before every refill, when every entry has
+// been popped, the wave commits the entries the last refill stored (flush_ring); after the loop
+// the lanes commit what they still hold and the wave flushes once more.  No LDS beyond the ring.
 // Ring layout, word-major (entry i of array k at [k * 64 + i]: a wave's lanes touch consecutive
 // words): od = origin.xyz, direction.xyz; meta = time word, pixel, sample, tagged tile pixel.
 RT_FN int wave_prefix(unsigned long long m) {  // set bits of m below this lane
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
+// One finished sample: its radiance to fixed point, the words added to its pool's slot or to
+// `accum` (the tagged tile pixel says which), a non-finite component flagged on its pixel
+template <class Work>
+RT_FN void commit_sample_ring(Work& work, int tpk, f3 L) {
+  Acc a;
+  acc_clear(a);
+  bool bad = false;
+  acc_sample(a, L, bad);
+  work.commit_ring(tpk, a, bad);
+}
+// Wave-collective, every lane of the wave active: the finished samples that popping lanes left in
+// the ring's entries [0, filled) (radiance in the origin's words, the sample's tag in the ray's; -1:
+// none), converted and committed at full width.  Entries at `filled` and above are an older
+// generation's, committed already: not read.
+template <class Work>
+RT_FN void flush_ring(Work& work, const real* ring_od, const uint32_t* ring_meta, int filled) {
+  constexpr int kN = RT_RING_LANES;
+  __builtin_amdgcn_wave_barrier();
+  const int i = (int)__lane_id();
+  if (i < filled) {
+    const int tag = (int)ring_meta[3 * kN + i];
+    if (tag != -1) commit_sample_ring(work, tag, mk3(ring_od[i], ring_od[kN + i], ring_od[2 * kN + i]));
+  }
+  __builtin_amdgcn_wave_barrier();
+}
 template <class Work>
 RT_FN void lane_loop_flat_ring(const KernelParams& P0, Work& work, real* ring_od, uint32_t* ring_meta) {
   constexpr int kN = RT_RING_LANES;
   int cnt = 0;           // entries [0, cnt) of the ring hold rays not yet started (wave-uniform)
+  int filled = 0;        // entries the last refill stored: popped ones hold finished samples (wave-uniform)
   bool drained = false;  // a refill met the end of the queues: nothing is left to claim (wave-uniform)
   bool alive = false;
   uint32_t pix = 0u;
-  int sample = 0, tpk = 0, seg = 0;
+  int sample = 0, tpk = -1, seg = 0;  // tpk of a lane not alive: the finished sample it holds in T (-1: none)
   f3 T = mk3(RL(1.), RL(1.), RL(1.));
   real apdf = RL(1.);
   RayCtx R;
@@ -2115,7 +2146,12 @@ RT_FN void lane_loop_flat_ring(const KernelParams& P0, Work& work, real* ring_od
           R.time_w = ring_meta[e];
           pix = ring_meta[kN + e];
           sample = (int)ring_meta[2 * kN + e];
+          // the sample this lane held takes the freed entry's place until the next refill (one lane
+          // per entry: no two lanes touch one)
+          const int held = tpk;
           tpk = (int)ring_meta[3 * kN + e];
+          ring_od[e] = T.x, ring_od[kN + e] = T.y, ring_od[2 * kN + e] = T.z;
+          ring_meta[3 * kN + e] = (uint32_t)held;
           R.self_gid = -1;
           T = mk3(RL(1.), RL(1.), RL(1.));
           seg = 0;
@@ -2126,8 +2162,10 @@ RT_FN void lane_loop_flat_ring(const KernelParams& P0, Work& work, real* ring_od
         want -= take;
         if (want == 0 || drained) break;
         // the ring is empty and lanes still wait: the next 64 samples of the wave's stream, every
-        // lane of the wave active (lanes leave the loop only once `drained`)
+        // lane of the wave active (lanes leave the loop only once `drained`).  First the samples
+        // the ring holds, so that a pool opened by the grab finds their slots' counts settled
         RT_PROF_ADD(PF_FRONT_LANES, kN);
+        flush_ring(work, ring_od, ring_meta, filled);
         int aslot;
         const int got = work.grab(true, aslot);
         const bool in = got < P.n_items;
@@ -2148,7 +2186,7 @@ RT_FN void lane_loop_flat_ring(const KernelParams& P0, Work& work, real* ring_od
           ring_meta[3 * kN + e] = (uint32_t)jt;
         }
         __builtin_amdgcn_wave_barrier();
-        cnt = (int)__popcll(vm);
+        filled = cnt = (int)__popcll(vm);
         drained = __ballot(in) != ~0ull;
       }
     }
@@ -2161,17 +2199,18 @@ RT_FN void lane_loop_flat_ring(const KernelParams& P0, Work& work, real* ring_od
     RT_PROF_MARK(PF_TRAV);
     f3 L = mk3(RL(0.), RL(0.), RL(0.));
     if (shade<0, false, false>(P, cf(P.prims), pix, sample, seg, C.t, C.prim, -1, R, L, T, -1, &apdf)) {
-      // the path ended (R, T and apdf are indeterminate until the next pop: shade's invariant): its
-      // sample's words go to the pixel's sums at once
-      Acc a;
-      acc_clear(a);
-      bool bad = false;
-      acc_sample(a, L, bad);
-      work.commit_ring(tpk, a, bad);
+      // the path ended (R, T and apdf are indeterminate until the next pop: shade's invariant): the
+      // lane keeps the sample's radiance in T, under tpk, and leaves it in the ring entry it pops
+      T = L;
       alive = false;
     }
     RT_PROF_MARK(PF_SHADE);
   }
+  // every lane is back (the queues drained, the ring empty): the sample each lane still holds, then
+  // the ones left in the ring since the last refill (once per wave, after the last RT_PROF_MARK:
+  // counted in no phase)
+  if (tpk != -1) commit_sample_ring(work, tpk, T);
+  flush_ring(work, ring_od, ring_meta, filled);
   RT_PROF_FLUSH
 }
 #endif
