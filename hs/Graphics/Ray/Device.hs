@@ -41,6 +41,8 @@ module Graphics.Ray.Device
   , renderOnDevice, deviceCount
     -- * Progressive rendering on a film (rt.h rt_film_*): stop when the noise is low enough
   , raytraceUntil, renderUntilOnDevice
+    -- * Adaptive: samples only where the film's noise estimate asks
+  , raytraceAdaptive, renderAdaptiveOnDevice
     -- * ... and a denoised preview of it (rt.h rt_denoise_*)
   , raytraceDenoised, renderDenoisedOnDevice
     -- * ... both over a device list (rt.h rt_multi_film_*: every GPU renders its rows of each pass, one frame)
@@ -572,6 +574,10 @@ foreign import ccall safe "rt_film_destroy"
   c_rt_film_destroy :: Ptr () -> IO CInt
 foreign import ccall safe "rt_film_add"
   c_rt_film_add :: Ptr () -> Int32 -> Ptr () -> IO CInt
+foreign import ccall safe "rt_adaptive_add"
+  c_rt_adaptive_add :: Ptr () -> Int32 -> CDouble -> Int32 -> Ptr () -> IO CInt
+foreign import ccall safe "rt_adaptive_get_info"
+  c_rt_adaptive_get_info :: Ptr () -> Ptr () -> IO CInt
 foreign import ccall safe "rt_film_read"
   c_rt_film_read :: Ptr () -> Ptr () -> IO CInt
 foreign import ccall safe "rt_film_noise"
@@ -1072,7 +1078,18 @@ hitMany (DeviceScene scene) queries =
 -- sample count.  The film lives on the first device of 'doDevices' (device 0 by default).
 renderUntilOnDevice :: DeviceOptions -> R.CameraSettings -> Geometry m Material -> StdGen -> Double -> Int
                     -> IO (Either RenderError (A.Matrix A.S Color, Int))
-renderUntilOnDevice = renderUntilWith filmImage
+renderUntilOnDevice = renderUntilWith uniformPasses filmImage
+
+-- | 'renderUntilOnDevice' with convergence per pixel (rt.h rt_adaptive_add): two uniform passes of
+-- @batch@ samples, then adaptive passes of @batch@ — each adds samples only to the pixels whose own
+-- relative error is above @target@ and whose count stays within cs_samplesPerPixel — until a pass
+-- selects nothing.  Every pixel is bit-identical to rt_render's at the pixel's own sample count;
+-- returns the image and the largest count.  Selection reads an estimate made from the pixel's own
+-- earlier samples, so the adaptive mean carries the usual small adaptive-sampling bias, which
+-- nothing corrects.  cs_samplesPerPixel must exceed @batch@ (two passes); one device.
+renderAdaptiveOnDevice :: DeviceOptions -> R.CameraSettings -> Geometry m Material -> StdGen -> Double -> Int
+                       -> IO (Either RenderError (A.Matrix A.S Color, Int))
+renderAdaptiveOnDevice = renderUntilWith adaptivePasses filmImage
 
 -- | 'renderUntilOnDevice' whose image is the film's denoised one (rt_denoise_features over 8
 -- samples, rt_denoise_albedo over 64, then rt_denoise_film_read with the library's default parameters): the preview of a
@@ -1080,13 +1097,15 @@ renderUntilOnDevice = renderUntilWith filmImage
 -- @batch@ (the library's RT_E_INVALID otherwise); one device, one shard.
 renderDenoisedOnDevice :: DeviceOptions -> R.CameraSettings -> Geometry m Material -> StdGen -> Double -> Int
                        -> IO (Either RenderError (A.Matrix A.S Color, Int))
-renderDenoisedOnDevice = renderUntilWith filmDenoised
+renderDenoisedOnDevice = renderUntilWith uniformPasses filmDenoised
 
--- | The passes of 'renderUntilOnDevice', then @readout precision film height width@.
-renderUntilWith :: (Precision -> Ptr () -> Int -> Int -> IO (Either RenderError (A.Matrix A.S Color)))
+-- | The passes @passes film maxSpp target batch@ on a one-device film ('uniformPasses': those of
+-- 'renderUntilOnDevice'; 'adaptivePasses'), then @readout precision film height width@.
+renderUntilWith :: (Ptr () -> Int -> Double -> Int -> IO (Either RenderError Int))
+                -> (Precision -> Ptr () -> Int -> Int -> IO (Either RenderError (A.Matrix A.S Color)))
                 -> DeviceOptions -> R.CameraSettings -> Geometry m Material -> StdGen -> Double -> Int
                 -> IO (Either RenderError (A.Matrix A.S Color, Int))
-renderUntilWith readout opts settings world gen target batch =
+renderUntilWith passes readout opts settings world gen target batch =
   case (geoDesc world, reifyBackground (R.cs_background settings)) of
     (Just desc, Just bg) -> do
       tagged <- tagShared desc
@@ -1108,8 +1127,7 @@ renderUntilWith readout opts settings world gen target batch =
                     rc1 <- c_rt_film_create scene cam (philoxKey gen) ex pfilm
                     r <- if rc1 /= 0 then libraryError rc1 else do
                       film <- peek pfilm
-                      done <- filmPasses (\n -> c_rt_film_add film n nullPtr) film (R.cs_samplesPerPixel settings) target
-                                         (max 1 batch)
+                      done <- passes film (R.cs_samplesPerPixel settings) target (max 1 batch)
                       out <- case done of
                         Left e -> pure (Left e)
                         Right spp -> fmap (\img -> (img, spp)) <$> readout (doPrecision opts) film h w
@@ -1200,6 +1218,29 @@ filmPasses add film maxSpp target batch = alloca $ \pnoise -> go pnoise 0 (0 :: 
                 if (realToFrac figure :: Double) <= target then pure (Right (spp + n))
                   else go pnoise (spp + n) (passes + 1)
 
+-- | 'filmPasses' on a one-device film: uniform passes (rt_film_add).
+uniformPasses :: Ptr () -> Int -> Double -> Int -> IO (Either RenderError Int)
+uniformPasses film = filmPasses (\n -> c_rt_film_add film n nullPtr) film
+
+-- | Two uniform passes of @batch@ samples, then adaptive passes (rt_adaptive_add film batch target
+-- maxSpp) until one selects nothing (rt_adaptive_info.selected, byte 16 of its 32); the largest
+-- per-pixel sample count (max_samples, byte 12).
+adaptivePasses :: Ptr () -> Int -> Double -> Int -> IO (Either RenderError Int)
+adaptivePasses film maxSpp target batch
+  | maxSpp <= batch = pure (Left (LibraryError (-2) "adaptive passes need two uniform passes first: cs_samplesPerPixel > batch"))
+  | otherwise = do
+      rc0 <- c_rt_film_add film (fromIntegral batch) nullPtr
+      rc1 <- if rc0 /= 0 then pure rc0 else c_rt_film_add film (fromIntegral (min batch (maxSpp - batch))) nullPtr
+      if rc1 /= 0 then libraryError rc1 else allocaBytes 32 go
+  where
+    go :: Ptr () -> IO (Either RenderError Int)
+    go info = do
+      rc <- c_rt_adaptive_add film (fromIntegral batch) (realToFrac target) (fromIntegral maxSpp) nullPtr
+      rci <- if rc /= 0 then pure rc else c_rt_adaptive_get_info film info
+      if rci /= 0 then libraryError rci else do
+        selected <- peekByteOff info 16 :: IO Int32
+        if selected > 0 then go info else (Right . fromIntegral) <$> (peekByteOff info 12 :: IO Int32)
+
 -- | The film's image (rt_film_read) as a storable matrix; FP32 films are widened to Double.
 filmImage :: Precision -> Ptr () -> Int -> Int -> IO (Either RenderError (A.Matrix A.S Color))
 filmImage = filmReadWith c_rt_film_read
@@ -1244,6 +1285,20 @@ raytraceUntil settings world gen noise batch =
     Left e | fallback e -> (R.raytrace settings (toReferenceRandom world) gen, R.cs_samplesPerPixel settings)
            | otherwise -> error ("Graphics.Ray.Device.raytraceUntil: the film failed: " ++ show e)
 {-# NOINLINE raytraceUntil #-}
+
+-- | 'raytraceUntil' with convergence per pixel ('renderAdaptiveOnDevice'): @raytraceAdaptive
+-- settings world gen noise batch@ adds samples only where a pixel's own relative error is above
+-- @noise@, up to cs_samplesPerPixel per pixel, and returns the image with the largest per-pixel
+-- sample count.  The fallback rules are 'raytrace''s; the CPU path has no film and renders all
+-- cs_samplesPerPixel samples.
+raytraceAdaptive :: R.ToRandom m => R.CameraSettings -> Geometry m Material -> StdGen -> Double -> Int
+                 -> (A.Matrix A.D Color, Int)
+raytraceAdaptive settings world gen noise batch =
+  case unsafePerformIO (renderAdaptiveOnDevice defaultDeviceOptions settings world gen noise batch) of
+    Right (img, spp) -> (A.delay img, spp)
+    Left e | fallback e -> (R.raytrace settings (toReferenceRandom world) gen, R.cs_samplesPerPixel settings)
+           | otherwise -> error ("Graphics.Ray.Device.raytraceAdaptive: the film failed: " ++ show e)
+{-# NOINLINE raytraceAdaptive #-}
 
 -- | 'raytraceUntil' over a device list, as 'raytraceWith' is 'raytrace''s: the passes are rendered
 -- by every device of 'doDevices' (default: every visible GPU) into one frame; the image and the

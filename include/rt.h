@@ -361,6 +361,56 @@ int rt_film_state_bytes(const rt_film* f, int64_t* bytes);
 int rt_film_save(const rt_film* f, void* host_buf, int64_t cap);
 int rt_film_load(rt_film* f, const void* host_buf, int64_t bytes);
 
+/* Adaptive film passes: add samples only where the film's own noise estimate asks for them.
+ *
+ * A film becomes NON-UNIFORM at its first rt_adaptive_add: it gains a count plane, two uint32 per
+ * tile pixel — the pixel's samples N_p and passes K_p —, allocated by that call (with the selection
+ * list and scratch; no later call allocates) and started at the film's (N, K) inside the frame and
+ * (0, 0) on a shard's padding rows.  A film that never makes the call allocates nothing more and
+ * behaves and saves bit for bit as before.
+ *
+ * rt_adaptive_add: enqueue one adaptive pass on hip_stream (asynchronous, no host synchronisation).
+ *   A pixel COUNTS if it lies inside the frame and is not NaN-flagged; a counting pixel is SELECTED
+ *   iff its relative error — what rt_film_noise maps, in binary64 before the cast to float, from the
+ *   pixel's own (N_p, K_p) — is > threshold (a negative threshold selects every counting pixel) and
+ *   N_p + n_samples <= max_samples (0: 2^24, the film's limit).  Every selected pixel receives
+ *   samples [N_p, N_p + n_samples) of its own stream — the key, events and arithmetic of a render, so
+ *   the pixel's sums, flag and colour are bit for bit those of a uniform film at N_p + n_samples —,
+ *   its estimator word one more batch, and (N_p, K_p) += (n_samples, 1).  Unselected pixels are not
+ *   touched.  The selection is taken in ascending tile-pixel order.  Needs two passes in the film;
+ *   RT_E_INVALID otherwise and for a null film, n_samples <= 0, a NaN threshold, max_samples outside
+ *   [0, 2^24] or a multi-device film's frame, each before any device call.
+ *   The threshold reads an estimate made from the pixel's own earlier samples, so the adaptive mean
+ *   carries the usual small adaptive-sampling bias; nothing here corrects it.
+ * On a non-uniform film: rt_film_resolve / rt_film_read divide each pixel by its own N_p (the
+ *   one-shot resolve's operation sequence); rt_film_noise uses each pixel's (N_p, K_p);
+ *   rt_film_get_info reports the largest N_p and K_p; rt_film_save writes layout version 2 — the
+ *   version-1 bytes, then the count plane, the header's samples / passes the maxima
+ *   (rt_film_state_bytes counts it) — and rt_film_load accepts versions 1 and 2, a version-2 state
+ *   making the film non-uniform.  rt_film_add is RT_E_INVALID (a uniform continuation is
+ *   rt_adaptive_add with a negative threshold), rt_denoise_film / rt_denoise_film_read are
+ *   RT_E_UNSUPPORTED (the filter's variance uses one N, K), rt_multi_film_load of a version-2 state
+ *   is RT_E_INVALID.  rt_film_reset drops the plane: the film is uniform again.
+ * The calls below are synchronous behind the film's last stream.
+ * rt_adaptive_get_info: the counts' summary.  rt_adaptive_counts_read: the plane, tile pixels x 2
+ *   uint32 (N_p, K_p); on a uniform film (N, K) inside the frame and (0, 0) on padding rows.
+ * rt_adaptive_selection_read: the last adaptive pass's selection, ascending tile pixels: *n its
+ *   length, the first min(cap, *n) entries written (host_tile_pixels may be NULL with cap 0);
+ *   *n = 0 when no adaptive pass has run since create, reset or load. */
+typedef struct rt_adaptive_info {
+  int64_t total_samples;   /* the sum of N_p over the pixels that count */
+  int32_t min_samples;     /* the smallest and ...                       */
+  int32_t max_samples;     /* ... largest N_p of a pixel that counts     */
+  int32_t selected;        /* pixels the last adaptive pass selected     */
+  int32_t adaptive_passes; /* since create, reset or load                */
+  int32_t nonuniform;      /* 1: the film holds a count plane            */
+  int32_t reserved;
+} rt_adaptive_info;
+int rt_adaptive_add(rt_film* f, int32_t n_samples, double threshold, int32_t max_samples, void* hip_stream);
+int rt_adaptive_get_info(const rt_film* f, rt_adaptive_info* info);
+int rt_adaptive_counts_read(const rt_film* f, uint32_t* host);
+int rt_adaptive_selection_read(const rt_film* f, int32_t* host_tile_pixels, int64_t cap, int64_t* n);
+
 /* Multi-device film: progressive passes over a multi-device scene's device list, ONE frame.
  *
  * The film holds one accumulation state, on the scene's first device: an ordinary one-shard film of

@@ -11,7 +11,7 @@ from .core import (V3, X, Y, Z, StdGen, allCorners, boxHull, boxJoin, component,
                    inInterval, longestDim, midpoint, mkStdGen, padBox, padInterval, reflect, shiftBox)
 from .denoise import denoise_reference, emitter_twin
 from .errors import RtDeviceError, RtError, RtInvalid, RtUnsupported
-from .film import Film, MultiFilm, noise_from_sums, raytrace_until
+from .film import Film, MultiFilm, noise_from_counts, noise_from_sums, raytrace_until
 from .geometry import (M44, Mesh, ObjParseError, boundingBox, bvhNode, bvhTree, constantMedium, cuboid, group,
                        moving, parallelogram, parseObj, pureGeometry, readObj, rotateX, rotateY, rotateZ, scale,
                        sphere, transform, transformVertices, translate, triangle, triangleMesh, withMaterial)

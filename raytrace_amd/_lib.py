@@ -22,6 +22,7 @@ EXPORTED = ["rt_abi_version", "rt_last_error", "rt_device_count", "rt_image_heig
             "rt_multi_scene_create", "rt_multi_scene_destroy", "rt_multi_render",
             "rt_film_create", "rt_film_destroy", "rt_film_reset", "rt_film_add", "rt_film_resolve", "rt_film_read",
             "rt_film_noise", "rt_film_get_info", "rt_film_state_bytes", "rt_film_save", "rt_film_load",
+            "rt_adaptive_add", "rt_adaptive_get_info", "rt_adaptive_counts_read", "rt_adaptive_selection_read",
             "rt_multi_film_create", "rt_multi_film_destroy", "rt_multi_film_reset", "rt_multi_film_add",
             "rt_multi_film_load", "rt_multi_film_frame", "rt_multi_film_copies",
             "rt_denoise_default_params", "rt_denoise_features", "rt_denoise_albedo", "rt_denoise_features_read", "rt_denoise_albedo_read", "rt_denoise_film",
@@ -89,6 +90,12 @@ class RtFilmInfo(ctypes.Structure):
                 ("rows", ctypes.c_int32), ("nan_pixels", ctypes.c_int32), ("f32", ctypes.c_int32)]
 
 
+class RtAdaptiveInfo(ctypes.Structure):
+    _fields_ = [("total_samples", ctypes.c_int64), ("min_samples", ctypes.c_int32), ("max_samples", ctypes.c_int32),
+                ("selected", ctypes.c_int32), ("adaptive_passes", ctypes.c_int32), ("nonuniform", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 class RtRay(ctypes.Structure):
     _fields_ = [("origin", ctypes.c_double * 3), ("dir", ctypes.c_double * 3), ("tmin", ctypes.c_double),
                 ("tmax", ctypes.c_double), ("time", ctypes.c_double), ("reserved", ctypes.c_double)]
@@ -151,6 +158,10 @@ def load():
     L.rt_film_state_bytes.argtypes = [P, ctypes.POINTER(ctypes.c_int64)]
     L.rt_film_save.argtypes = [P, P, ctypes.c_int64]
     L.rt_film_load.argtypes = [P, P, ctypes.c_int64]
+    L.rt_adaptive_add.argtypes = [P, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, P]
+    L.rt_adaptive_get_info.argtypes = [P, ctypes.POINTER(RtAdaptiveInfo)]
+    L.rt_adaptive_counts_read.argtypes = [P, P]
+    L.rt_adaptive_selection_read.argtypes = [P, P, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     L.rt_multi_film_create.argtypes = [P, ctypes.POINTER(RtCameraSettings), ctypes.c_uint64, ctypes.POINTER(RtExec),
                                        ctypes.POINTER(ctypes.c_void_p)]
     L.rt_multi_film_destroy.argtypes = [P]

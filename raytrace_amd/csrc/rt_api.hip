@@ -4,7 +4,8 @@
 // concurrent uploads, shard renders on per-device streams, a device-side gather by peer copies
 // into the first device's framebuffer and ONE device-to-host copy), the 8-bit output epilogue,
 // the progressive film (its state and entry points; kernels in rt_film.hip) and the multi-device
-// film (one frame film on the first device, a pass workspace per shard), error reporting.
+// film (one frame film on the first device, a pass workspace per shard), adaptive film passes (the
+// count plane and entry points; kernels in rt_adaptive.hip and rt_list*.hip), error reporting.
 // A synchronous render (render_sync) runs render_one (one device) or render_many (a thread per
 // shard) over the same stages: prepare_part, enqueue_shard, enqueue_readback, fill_stats.
 #include <hip/hip_runtime.h>
@@ -22,6 +23,7 @@
 #include <vector>
 
 #include "../../include/rt.h"
+#include "rt_adaptive.h"
 #include "rt_denoise.h"
 #include "rt_film.h"
 #include "rt_internal.h"
@@ -180,7 +182,8 @@ struct FilmHeader {  // the saved state's header (rt_film_save); totals, flags a
 };
 static_assert(sizeof(FilmHeader) == 64, "the saved film header is 64 bytes");
 constexpr uint32_t kFilmMagic = 0x4d4c4652u;  // "RFLM"
-constexpr uint32_t kFilmVersion = 1;
+constexpr uint32_t kFilmVersion = 1;          // a uniform film: header, totals, flags, q
+constexpr uint32_t kFilmVersionCounts = 2;    // a non-uniform film: those, then the count plane; header samples / passes: the maxima
 struct rt_film {
   const rt_device_scene* scene = nullptr;
   rt_camera_settings cs{};
@@ -213,6 +216,18 @@ struct rt_film {
   double* dn_mem = nullptr;            // ev[2][4] and guide[8] planes of n_pixels doubles
   bool owned = false;                  // a multi-device film's frame: rt_film_add / load / reset / destroy refuse it
   hipEvent_t e_order = nullptr;        // ... and its event: a new `last` stream waits for the one before (film_follow)
+  // adaptive passes (rt_adaptive.h): one allocation of its own, made by the first rt_adaptive_add (or
+  // the load of a version-2 state) and kept — the count plane, the selection list and its length
+  // word, the select kernels' scratch.  While `nonuniform`, samples / passes above are not read:
+  // the counts are the plane's
+  char* ad_mem = nullptr;
+  uint32_t* counts = nullptr;          // 2 x uint32 per tile pixel: N_p, K_p
+  rt_adaptive_rec* ad_list = nullptr;  // the last pass's selection, ascending tile pixels
+  int* ad_n = nullptr;                 // ... and its length
+  void* ad_scratch = nullptr;
+  bool nonuniform = false;
+  bool ad_listed = false;              // ad_list / ad_n hold a pass's selection
+  int32_t adaptive_passes = 0;
 };
 
 // A multi-device film (include/rt.h rt_multi_film_*): ONE accumulation state — `frame`, an ordinary
@@ -799,10 +814,14 @@ FilmHeader film_header(const rt_film* f) {
   h.samples = f->samples;
   return h;
 }
-// the saved state: header, totals, flags, q (unpadded)
+// the saved state: header, totals, flags, q (unpadded); a non-uniform film's: then the count plane
 size_t film_sums_bytes(const rt_film* f) { return f->n_pixels * f->acc_words * sizeof(long long); }
-int64_t film_state_bytes(const rt_film* f) {
+size_t film_counts_bytes(const rt_film* f) { return f->n_pixels * 2 * sizeof(uint32_t); }
+int64_t film_state_bytes_v1(const rt_film* f) {
   return (int64_t)(sizeof(FilmHeader) + film_sums_bytes(f) + f->n_pixels * (sizeof(unsigned) + sizeof(double)));
+}
+int64_t film_state_bytes(const rt_film* f) {
+  return film_state_bytes_v1(f) + (f->nonuniform ? (int64_t)film_counts_bytes(f) : 0);
 }
 void film_destroy(rt_film* f) {
   if (!f) return;
@@ -813,8 +832,83 @@ void film_destroy(rt_film* f) {
     (void)hipFree(f->feat);
     (void)hipFree(f->feat2);
     (void)hipFree(f->dn_mem);
+    (void)hipFree(f->ad_mem);
   }
   delete f;
+}
+
+// ---- adaptive passes (rt_adaptive.h)
+
+// the buffers of the adaptive passes, allocated once (the film's device is current)
+int adaptive_alloc(rt_film* f) {
+  if (f->ad_mem) return RT_OK;
+  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t cb = pad(film_counts_bytes(f)), lb = pad(f->n_pixels * sizeof(rt_adaptive_rec)), nb = 256;
+  HIP_TRY(hipMalloc((void**)&f->ad_mem, cb + lb + nb + pad(rt_adaptive_scratch_bytes((long long)f->n_pixels))));
+  char* p = f->ad_mem;
+  f->counts = (uint32_t*)p, p += cb;
+  f->ad_list = (rt_adaptive_rec*)p, p += lb;
+  f->ad_n = (int*)p, p += nb;
+  f->ad_scratch = p;
+  return RT_OK;
+}
+// what the count plane says about a non-uniform film, read behind f->last (synchronous; f->mu held)
+struct CountStats {
+  int64_t total = 0;  // the sum of N_p over the pixels that count
+  uint32_t min_n = 0, max_n = 0, max_k = 0;
+};
+int adaptive_stats(const rt_film* f, CountStats& st, std::vector<uint32_t>* counts_out = nullptr) {
+  std::vector<uint32_t> c(2 * f->n_pixels);
+  std::vector<unsigned> flags(f->n_pixels);
+  HIP_TRY(hipSetDevice(f->scene->device));
+  HIP_TRY(hipMemcpyAsync(c.data(), f->counts, film_counts_bytes(f), hipMemcpyDeviceToHost, f->last));
+  HIP_TRY(hipMemcpyAsync(flags.data(), f->flags, f->n_pixels * sizeof(unsigned), hipMemcpyDeviceToHost, f->last));
+  HIP_TRY(hipStreamSynchronize(f->last));
+  bool any = false;
+  for (size_t p = 0; p < f->n_pixels; ++p) {
+    st.max_n = std::max(st.max_n, c[2 * p]);
+    st.max_k = std::max(st.max_k, c[2 * p + 1]);
+    if (flags[p] || !rt_adaptive_inside((long long)p, f->width, f->height, f->ex.n_shards, f->ex.shard, f->ex.row_block))
+      continue;
+    st.total += c[2 * p];
+    st.min_n = any ? std::min(st.min_n, c[2 * p]) : c[2 * p];
+    any = true;
+  }
+  if (counts_out) counts_out->swap(c);
+  return RT_OK;
+}
+// one adaptive pass of precision R on st: select, the zeroed workspace, the list kernel, the merge
+template <class R>
+int adaptive_pass(rt_film* f, int n_samples, double threshold, long long max_samples, hipStream_t st) {
+  const rt_device_scene* s = f->scene;
+  if (int rc = ensure_precision<R>(s)) return rc;
+  LaunchInputs L;
+  L.resident_lanes = 4096;  // (the work plan is the render's; the list kernel has its own)
+  L.lds_nodes = 0;          // no staged nodes: every node from memory
+  rt_camera_settings cs = f->cs;
+  cs.samples_per_pixel = n_samples;
+  KernelParamsT<R> P;
+  std::string err;
+  if (int rc = rt_host_render_params(*s->host, s->variant, s->arrays<R>().rec, &cs, f->seed, &f->ex, L, P, err))
+    return fail(rc, "%s", err.c_str());
+  P.status = s->status;
+  P.accum = (unsigned long long*)f->ws;
+  P.nanflag = (unsigned int*)(f->ws + f->ws_lay.off_flag);
+  P.counter = (int*)(f->ws + f->ws_lay.off_ctr);
+  int chunk = 0;  // (experiments and tests: samples per item; the state does not depend on it)
+  if (const char* e = rt_knob("RT_AMD_LIST_CHUNK")) chunk = std::max(0, atoi(e));
+  const long long np = (long long)f->n_pixels;
+  if (rt_adaptive_launch_select(f->total, f->flags, f->q, f->counts, np, f->acc_words, n_samples, threshold, max_samples,
+                                f->width, f->height, f->ex.n_shards, f->ex.shard, f->ex.row_block, f->ad_scratch, f->ad_list,
+                                f->ad_n, st))
+    return fail(RT_E_HIP, "select launch failed: %s", hipGetErrorString(hipGetLastError()));
+  HIP_TRY(hipMemsetAsync(f->ws, 0, f->ws_lay.bytes, st));
+  if (rt_launch_list(P, s->variant, f->ad_list, f->ad_n, n_samples, chunk, st))
+    return fail(RT_E_HIP, "list kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+  if (rt_adaptive_launch_merge(f->total, f->flags, f->q, f->counts, P.accum, P.nanflag, f->ad_list, f->ad_n, np, f->acc_words,
+                               n_samples, st))
+    return fail(RT_E_HIP, "list merge launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return RT_OK;
 }
 // A multi-device film's frame is read like any film, but only the multi film adds to it, loads,
 // resets and destroys it (rt_multi_film_*): rt_film_add / load / reset / destroy refuse it
@@ -851,6 +945,11 @@ int film_resolve(const rt_film* f, void* d_out, hipStream_t st) {
 int film_resolve_any(const rt_film* f, void* d_out, hipStream_t st) {
   if (f->samples <= 0) return fail(RT_E_INVALID, "the film holds no samples");
   HIP_TRY(hipSetDevice(f->scene->device));
+  if (f->nonuniform) {  // each pixel's mean over its own N_p (rt_adaptive.h)
+    if (rt_adaptive_launch_resolve(f->total, f->flags, f->counts, d_out, (long long)f->n_pixels, f->f32, st))
+      return fail(RT_E_HIP, "resolve launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return RT_OK;
+  }
   return f->f32 ? film_resolve<float>(f, d_out, st) : film_resolve<double>(f, d_out, st);
 }
 
@@ -940,6 +1039,10 @@ int denoise_check(const rt_film* f, const rt_denoise_params* p) {
   if (f->ex.n_shards > 1)
     return fail(RT_E_UNSUPPORTED, "a film of %d shards holds interleaved rows: the filter needs a pixel's neighbours",
                 f->ex.n_shards);
+  if (f->nonuniform)
+    return fail(RT_E_UNSUPPORTED,
+                "the film is non-uniform (adaptive passes): the filter's variance uses one sample and pass count for every "
+                "pixel; denoise a uniform film, or rt_film_reset this one");
   if (f->passes < 2) return fail(RT_E_INVALID, "the denoiser's variance needs two passes (the film has %d)", f->passes);
   if (f->feat_samples <= 0) return fail(RT_E_INVALID, "the film's features have not been computed (rt_denoise_features)");
   return RT_OK;
@@ -1159,6 +1262,9 @@ int film_reset(rt_film* f) {
   HIP_TRY(hipStreamSynchronize(f->last));
   f->samples = 0;
   f->passes = 0;
+  f->nonuniform = false;  // the count plane is dropped (its allocation is kept for the next adaptive pass)
+  f->ad_listed = false;
+  f->adaptive_passes = 0;
   return RT_OK;
 }
 }  // namespace
@@ -1174,6 +1280,11 @@ int rt_film_add(rt_film* f, int32_t n_samples, void* hip_stream) {
   if (int rc = refuse_owned(f, "rt_film_add")) return rc;
   if (n_samples <= 0) return fail(RT_E_INVALID, "a pass adds at least one sample (%d)", n_samples);
   std::lock_guard<std::mutex> lock(f->mu);
+  if (f->nonuniform)
+    return fail(RT_E_INVALID,
+                "rt_film_add: the film is non-uniform (adaptive passes); rt_adaptive_add with a negative threshold adds "
+                "%d samples to every pixel",
+                n_samples);
   if (f->samples + n_samples > RT_FILM_MAX_SAMPLES)
     return fail(RT_E_INVALID, "a film holds at most 2^24 samples per pixel (%lld + %d)", (long long)f->samples, n_samples);
   rt_camera_settings cs = f->cs;
@@ -1227,9 +1338,12 @@ int rt_film_noise(const rt_film* f, float* d_map_or_null, double* noise) {
   std::lock_guard<std::mutex> lock(const_cast<rt_film*>(f)->mu);  // (the partials are the film's scratch)
   if (f->passes < 2) return fail(RT_E_INVALID, "a noise estimate needs two passes (the film has %d)", f->passes);
   HIP_TRY(hipSetDevice(f->scene->device));
-  if (rt_film_launch_noise(f->total, f->flags, f->q, d_map_or_null, f->partial_sum, f->partial_cnt,
-                           (long long)f->n_pixels, f->acc_words, f->samples, f->passes, f->width, f->height,
-                           f->ex.n_shards, f->ex.shard, f->ex.row_block, f->last))
+  if (f->nonuniform ? rt_adaptive_launch_noise(f->total, f->flags, f->q, f->counts, d_map_or_null, f->partial_sum,
+                                               f->partial_cnt, (long long)f->n_pixels, f->acc_words, f->width, f->height,
+                                               f->ex.n_shards, f->ex.shard, f->ex.row_block, f->last)
+                    : rt_film_launch_noise(f->total, f->flags, f->q, d_map_or_null, f->partial_sum, f->partial_cnt,
+                                           (long long)f->n_pixels, f->acc_words, f->samples, f->passes, f->width, f->height,
+                                           f->ex.n_shards, f->ex.shard, f->ex.row_block, f->last))
     return fail(RT_E_HIP, "noise launch failed: %s", hipGetErrorString(hipGetLastError()));
   const size_t blocks = (size_t)rt_film_blocks((long long)f->n_pixels);
   std::vector<double> ps(blocks);
@@ -1253,6 +1367,12 @@ int rt_film_get_info(const rt_film* f, rt_film_info* info) {
   HIP_TRY(hipStreamSynchronize(f->last));
   info->samples = f->samples;
   info->passes = f->passes;
+  if (f->nonuniform) {  // the largest N_p and K_p
+    CountStats cst;
+    if (int rc = adaptive_stats(f, cst)) return rc;
+    info->samples = cst.max_n;
+    info->passes = (int32_t)cst.max_k;
+  }
   info->width = f->width;
   info->rows = f->rows;
   info->nan_pixels = (int32_t)std::count_if(flags.begin(), flags.end(), [](unsigned v) { return v != 0u; });
@@ -1271,8 +1391,17 @@ int rt_film_save(const rt_film* f, void* host_buf, int64_t cap) {
   std::lock_guard<std::mutex> lock(const_cast<rt_film*>(f)->mu);
   if (cap < film_state_bytes(f))
     return fail(RT_E_INVALID, "the film's state takes %lld bytes (buffer: %lld)", (long long)film_state_bytes(f), (long long)cap);
-  const FilmHeader h = film_header(f);
+  FilmHeader h = film_header(f);
   char* p = (char*)host_buf;
+  if (f->nonuniform) {  // layout version 2: the count plane behind the version-1 bytes, the maxima in the header
+    CountStats cst;
+    std::vector<uint32_t> counts;
+    if (int rc = adaptive_stats(f, cst, &counts)) return rc;
+    h.version = kFilmVersionCounts;
+    h.samples = cst.max_n;
+    h.passes = (int32_t)cst.max_k;
+    std::memcpy(p + film_state_bytes_v1(f), counts.data(), film_counts_bytes(f));
+  }
   std::memcpy(p, &h, sizeof h), p += sizeof h;
   HIP_TRY(hipSetDevice(f->scene->device));
   HIP_TRY(hipMemcpyAsync(p, f->total, film_sums_bytes(f), hipMemcpyDeviceToHost, f->last));
@@ -1285,13 +1414,19 @@ int rt_film_save(const rt_film* f, void* host_buf, int64_t cap) {
 }
 
 namespace {
-int film_load(rt_film* f, const void* host_buf, int64_t bytes) {
+// counts_ok: a version-2 state (a non-uniform film's) is accepted and makes the film non-uniform
+int film_load(rt_film* f, const void* host_buf, int64_t bytes, bool counts_ok) {
   std::lock_guard<std::mutex> lock(f->mu);
   if (bytes < (int64_t)sizeof(FilmHeader)) return fail(RT_E_INVALID, "not a saved film (%lld bytes)", (long long)bytes);
   FilmHeader h;
   std::memcpy(&h, host_buf, sizeof h);
-  if (h.magic != kFilmMagic || h.version != kFilmVersion)
-    return fail(RT_E_INVALID, "not a saved film of layout version %u", kFilmVersion);
+  if (h.magic != kFilmMagic || (h.version != kFilmVersion && h.version != kFilmVersionCounts))
+    return fail(RT_E_INVALID, "not a saved film of layout version %u or %u", kFilmVersion, kFilmVersionCounts);
+  const bool v2 = h.version == kFilmVersionCounts;
+  if (v2 && !counts_ok)
+    return fail(RT_E_INVALID,
+                "the saved film is non-uniform (layout version 2, adaptive passes): a multi-device film has no adaptive "
+                "passes; load it into a one-device rt_film");
   const FilmHeader w = film_header(f);
   if (h.f32 != w.f32 || h.width != w.width || h.height != w.height || h.rows != w.rows || h.n_shards != w.n_shards ||
       h.shard != w.shard || h.row_block != w.row_block || h.key0 != w.key0 || h.key1 != w.key1)
@@ -1300,12 +1435,28 @@ int film_load(rt_film* f, const void* host_buf, int64_t bytes) {
                 "%dx%d, shard %d of %d by %d rows, key %08x%08x)",
                 h.f32 ? "f32" : "f64", h.width, h.height, h.shard, h.n_shards, h.row_block, h.key1, h.key0,
                 w.f32 ? "f32" : "f64", w.width, w.height, w.shard, w.n_shards, w.row_block, w.key1, w.key0);
-  if (bytes != film_state_bytes(f) || h.samples < 0 || h.samples > RT_FILM_MAX_SAMPLES || h.passes < 0 ||
-      h.passes > h.samples)
+  const int64_t want = film_state_bytes_v1(f) + (v2 ? (int64_t)film_counts_bytes(f) : 0);
+  if (bytes != want || h.samples < 0 || h.samples > RT_FILM_MAX_SAMPLES || h.passes < 0 || h.passes > h.samples)
     return fail(RT_E_INVALID, "the saved film is damaged (%lld bytes, %lld samples, %d passes)", (long long)bytes,
                 (long long)h.samples, h.passes);
   const char* p = (const char*)host_buf + sizeof h;
   HIP_TRY(hipSetDevice(f->scene->device));
+  if (v2) {  // the count plane: every pixel within the header's maxima, a padding row empty
+    std::vector<uint32_t> c(2 * f->n_pixels);
+    std::memcpy(c.data(), (const char*)host_buf + film_state_bytes_v1(f), film_counts_bytes(f));
+    for (size_t i = 0; i < f->n_pixels; ++i) {
+      const bool in = rt_adaptive_inside((long long)i, f->width, f->height, f->ex.n_shards, f->ex.shard, f->ex.row_block);
+      const uint32_t N = c[2 * i], K = c[2 * i + 1];
+      if (in ? (K < 2 || K > N || (int64_t)N > h.samples || (int64_t)K > h.passes) : (N != 0 || K != 0))
+        return fail(RT_E_INVALID, "the saved film's count plane is damaged (tile pixel %zu: %u samples, %u passes)", i, N, K);
+    }
+    if (int rc = adaptive_alloc(f)) return rc;
+    HIP_TRY(hipMemcpyAsync(f->counts, c.data(), film_counts_bytes(f), hipMemcpyHostToDevice, f->last));
+    HIP_TRY(hipStreamSynchronize(f->last));  // (c is this call's)
+  }
+  f->nonuniform = v2;
+  f->ad_listed = false;
+  f->adaptive_passes = 0;
   HIP_TRY(hipMemcpyAsync(f->total, p, film_sums_bytes(f), hipMemcpyHostToDevice, f->last));
   p += film_sums_bytes(f);
   HIP_TRY(hipMemcpyAsync(f->flags, p, f->n_pixels * sizeof(unsigned), hipMemcpyHostToDevice, f->last));
@@ -1321,7 +1472,115 @@ int film_load(rt_film* f, const void* host_buf, int64_t bytes) {
 int rt_film_load(rt_film* f, const void* host_buf, int64_t bytes) {
   if (!f || !host_buf) return fail(RT_E_INVALID, "null argument");
   if (int rc = refuse_owned(f, "rt_film_load")) return rc;
-  return film_load(f, host_buf, bytes);
+  return film_load(f, host_buf, bytes, true);
+}
+
+// ---- adaptive film passes
+
+int rt_adaptive_add(rt_film* f, int32_t n_samples, double threshold, int32_t max_samples, void* hip_stream) {
+  if (!f) return fail(RT_E_INVALID, "null argument");
+  if (n_samples <= 0) return fail(RT_E_INVALID, "a pass adds at least one sample (%d)", n_samples);
+  if (threshold != threshold) return fail(RT_E_INVALID, "the threshold is NaN");
+  if (max_samples < 0 || max_samples > RT_FILM_MAX_SAMPLES)
+    return fail(RT_E_INVALID, "max_samples: 0 (2^24, the film's limit) to 2^24 (%d)", max_samples);
+  if (int rc = refuse_owned(f, "rt_adaptive_add")) return rc;
+  std::lock_guard<std::mutex> lock(f->mu);
+  if (f->passes < 2)
+    return fail(RT_E_INVALID, "an adaptive pass selects by the noise estimate, which needs two passes (the film has %d)",
+                f->passes);
+  // (the list kernel's item ids stay below 2^31: rt_list_kernel.h)
+  if ((long long)f->n_pixels * n_samples > 0x7fffffffLL - (1 << 20))
+    return fail(RT_E_INVALID, "an adaptive pass of %d samples over %zu pixels is too large (pixels x samples < 2^31)",
+                n_samples, f->n_pixels);
+  const long long cap = max_samples ? max_samples : RT_FILM_MAX_SAMPLES;
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIP_TRY(hipSetDevice(f->scene->device));
+  if (int rc = adaptive_alloc(f)) return rc;  // (the first call only)
+  if (!f->nonuniform) {
+    if (rt_adaptive_launch_init(f->counts, (long long)f->n_pixels, (uint32_t)f->samples, (uint32_t)f->passes, f->width,
+                                f->height, f->ex.n_shards, f->ex.shard, f->ex.row_block, st))
+      return fail(RT_E_HIP, "count plane launch failed: %s", hipGetErrorString(hipGetLastError()));
+    f->nonuniform = true;
+  }
+  f->last = st;
+  f->ad_listed = false;
+  if (int rc = f->f32 ? adaptive_pass<float>(f, n_samples, threshold, cap, st)
+                      : adaptive_pass<double>(f, n_samples, threshold, cap, st))
+    return rc;
+  f->ad_listed = true;
+  f->adaptive_passes += 1;
+  return RT_OK;
+}
+
+int rt_adaptive_get_info(const rt_film* f, rt_adaptive_info* info) {
+  if (!f || !info) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(const_cast<rt_film*>(f)->mu);
+  std::memset(info, 0, sizeof *info);
+  info->nonuniform = f->nonuniform;
+  info->adaptive_passes = f->adaptive_passes;
+  HIP_TRY(hipSetDevice(f->scene->device));
+  if (f->nonuniform) {
+    CountStats cst;
+    if (int rc = adaptive_stats(f, cst)) return rc;
+    info->total_samples = cst.total;
+    info->min_samples = (int32_t)cst.min_n;
+    info->max_samples = (int32_t)cst.max_n;
+  } else {  // every pixel that counts holds the film's N
+    std::vector<unsigned> flags(f->n_pixels);
+    HIP_TRY(hipMemcpyAsync(flags.data(), f->flags, f->n_pixels * sizeof(unsigned), hipMemcpyDeviceToHost, f->last));
+    HIP_TRY(hipStreamSynchronize(f->last));
+    int64_t counting = 0;
+    for (size_t p = 0; p < f->n_pixels; ++p)
+      counting += !flags[p] &&
+                  rt_adaptive_inside((long long)p, f->width, f->height, f->ex.n_shards, f->ex.shard, f->ex.row_block);
+    info->total_samples = counting * f->samples;
+    info->min_samples = info->max_samples = (int32_t)f->samples;
+  }
+  if (f->ad_listed) {
+    int n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, f->ad_n, sizeof n, hipMemcpyDeviceToHost, f->last));
+    HIP_TRY(hipStreamSynchronize(f->last));
+    info->selected = n;
+  }
+  return RT_OK;
+}
+
+int rt_adaptive_counts_read(const rt_film* f, uint32_t* host) {
+  if (!f || !host) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(const_cast<rt_film*>(f)->mu);
+  HIP_TRY(hipSetDevice(f->scene->device));
+  if (f->nonuniform) {
+    HIP_TRY(hipMemcpyAsync(host, f->counts, film_counts_bytes(f), hipMemcpyDeviceToHost, f->last));
+    HIP_TRY(hipStreamSynchronize(f->last));
+    return RT_OK;
+  }
+  // a uniform film: (N, K) inside the frame, (0, 0) on a shard's padding rows — what the plane would start as
+  for (size_t p = 0; p < f->n_pixels; ++p) {
+    const bool in = rt_adaptive_inside((long long)p, f->width, f->height, f->ex.n_shards, f->ex.shard, f->ex.row_block);
+    host[2 * p] = in ? (uint32_t)f->samples : 0u;
+    host[2 * p + 1] = in ? (uint32_t)f->passes : 0u;
+  }
+  return RT_OK;
+}
+
+int rt_adaptive_selection_read(const rt_film* f, int32_t* host_tile_pixels, int64_t cap, int64_t* n) {
+  if (!f || !n || cap < 0 || (cap > 0 && !host_tile_pixels)) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(const_cast<rt_film*>(f)->mu);
+  *n = 0;
+  if (!f->ad_listed) return RT_OK;  // no adaptive pass since create / reset / load
+  HIP_TRY(hipSetDevice(f->scene->device));
+  int count = 0;
+  HIP_TRY(hipMemcpyAsync(&count, f->ad_n, sizeof count, hipMemcpyDeviceToHost, f->last));
+  HIP_TRY(hipStreamSynchronize(f->last));
+  if (count < 0 || (size_t)count > f->n_pixels) return fail(RT_E_GENERIC, "the selection's length word is damaged (%d)", count);
+  *n = count;
+  const size_t take = (size_t)std::min<int64_t>(cap, count);
+  if (!take) return RT_OK;
+  std::vector<rt_adaptive_rec> recs(take);
+  HIP_TRY(hipMemcpyAsync(recs.data(), f->ad_list, take * sizeof(rt_adaptive_rec), hipMemcpyDeviceToHost, f->last));
+  HIP_TRY(hipStreamSynchronize(f->last));
+  for (size_t i = 0; i < take; ++i) host_tile_pixels[i] = recs[i].tp;
+  return RT_OK;
 }
 
 // ---- multi-device film
@@ -1522,7 +1781,7 @@ int rt_multi_film_load(rt_multi_film* f, const void* host_buf, int64_t bytes) {
   if (!f || !host_buf) return fail(RT_E_INVALID, "null argument");
   std::lock_guard<std::mutex> lock(f->mu);
   if (int rc = multi_film_wait(f)) return rc;
-  return film_load(f->frame, host_buf, bytes);
+  return film_load(f->frame, host_buf, bytes, false);
 }
 
 int rt_multi_film_frame(rt_multi_film* f, rt_film** frame) {

@@ -533,6 +533,15 @@ int rt_launch_query(const KernelParams& p, int variant, const rt_ray* rays, rt_h
                     int flags, void* stream);
 int rt_launch_query(const KernelParams64& p, int variant, const rt_ray* rays, rt_hit* hits, const int* prim_mat,
                     long long n, int flags, void* stream);
+// rt_list.hip / rt_list64_nl.hip: samples [N_p, N_p + n_samples) of the *n_list listed tile pixels
+// (rt_adaptive.h rt_adaptive_rec; device pointers) added to p.accum / p.nanflag, a zeroed pass
+// workspace whose p.counter[0] is the kernel's zeroed item cursor (rt_list_kernel.h).  p as a
+// render's (rt_host_render_params) with lds_nodes = 0 and status set; chunk > 0: samples per item
+struct rt_adaptive_rec;
+int rt_launch_list(const KernelParams& p, int variant, const rt_adaptive_rec* list, const int* n_list, int n_samples,
+                   int chunk, void* stream);
+int rt_launch_list(const KernelParams64& p, int variant, const rt_adaptive_rec* list, const int* n_list, int n_samples,
+                   int chunk, void* stream);
 #if defined(RT_PHASE_PROF)
 int rt_prof_read_kernel(const KernelParams*, unsigned long long* out, int n);
 int rt_prof_read_kernel(const KernelParams64*, unsigned long long* out, int n);

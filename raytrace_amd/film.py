@@ -13,7 +13,10 @@ of a, b, c samples give exactly the image of `raytrace` at a + b + c samples per
 
 `raytrace_until` is that loop as one call.  `noise_from_sums` restates the estimator in numpy.
 `film.denoised()` is the image filtered for a preview and `film.features()` its guide buffers
-(raytrace_amd.denoise).  `MultiFilm(world, settings, seed, devices=[0, 1, ...])` is the same film
+(raytrace_amd.denoise).  `film.add_where(n, threshold)` adds samples only to the pixels whose own
+noise estimate is above a threshold (an adaptive pass; `film.sample_map()` is the per-pixel count,
+`raytrace_until(..., adaptive=True)` the loop, `noise_from_counts` the estimator with per-pixel
+counts in numpy).  `MultiFilm(world, settings, seed, devices=[0, 1, ...])` is the same film
 rendered by several GPUs into one frame; `raytrace_until(..., devices=[...])` runs on it.
 """
 from __future__ import annotations
@@ -96,8 +99,55 @@ class Film:
         _lib.check(self._lib.rt_film_add(self.handle, int(n), ctypes.c_void_p(stream_ptr or None)))
         return self
 
+    def add_where(self, n: int, threshold: float, max_spp: int | None = None, stream_ptr: int = 0):
+        """Enqueue an adaptive pass (rt_adaptive_add; asynchronous; returns self): samples [N_p, N_p + n)
+        of every pixel that counts (inside the frame, not NaN-flagged), whose relative error
+        (noise_from_counts: noise_map's value in binary64) is > threshold and whose count N_p + n stays
+        within max_spp (None: the film's limit, 2^24).  A negative threshold selects every such pixel.
+        The film needs two passes.  From the first call on the film is non-uniform: .spp and .passes
+        are the per-pixel maxima, sample_map() the counts, state() layout version 2, add() and
+        denoised() raise (RtInvalid / RtUnsupported) until reset().  A selected pixel's colour is bit
+        for bit a uniform film's at its count; selection reads the pixel's own earlier samples, so
+        the adaptive mean carries the usual small adaptive-sampling bias, which nothing corrects."""
+        _lib.check(self._lib.rt_adaptive_add(self.handle, int(n), float(threshold), int(max_spp or 0),
+                                             ctypes.c_void_p(stream_ptr or None)))
+        return self
+
+    def counts(self) -> np.ndarray:
+        """(rows, width, 2) uint32: each pixel's samples N_p and passes K_p ((spp, passes) on a uniform
+        film; (0, 0) on a shard's padding rows)."""
+        self._ready()
+        c = np.zeros(self.shape[:2] + (2,), np.uint32)
+        _lib.check(self._lib.rt_adaptive_counts_read(self.handle, c.ctypes.data_as(ctypes.c_void_p)))
+        return c
+
+    def sample_map(self) -> np.ndarray:
+        """(rows, width) uint32: the samples each pixel holds."""
+        return np.ascontiguousarray(self.counts()[..., 0])
+
+    def selection(self) -> np.ndarray:
+        """The tile pixels (row * width + column, ascending) the last add_where selected: int32."""
+        self._ready()
+        n = ctypes.c_int64()
+        _lib.check(self._lib.rt_adaptive_selection_read(self.handle, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, np.int32)
+        if n.value:
+            _lib.check(self._lib.rt_adaptive_selection_read(self.handle, out.ctypes.data_as(ctypes.c_void_p), n.value,
+                                                            ctypes.byref(n)))
+        return out
+
+    def adaptive_info(self) -> dict:
+        """total_samples (over the pixels that count), min_samples, max_samples, selected (by the last
+        add_where), adaptive_passes and nonuniform (rt_adaptive_get_info)."""
+        self._ready()
+        st = _lib.RtAdaptiveInfo()
+        _lib.check(self._lib.rt_adaptive_get_info(self.handle, ctypes.byref(st)))
+        return dict(total_samples=st.total_samples, min_samples=st.min_samples, max_samples=st.max_samples,
+                    selected=st.selected, adaptive_passes=st.adaptive_passes, nonuniform=bool(st.nonuniform))
+
     def image(self, out: np.ndarray | None = None) -> np.ndarray:
-        """The mean of the samples so far: (rows, width, 3) linear RGB, as `raytrace` at .spp."""
+        """The mean of the samples so far: (rows, width, 3) linear RGB, as `raytrace` at .spp (a
+        non-uniform film: each pixel as `raytrace` at its own count)."""
         from .ray import _out_buffer
         self._ready()
         out = _out_buffer(out, self.shape, self.dtype)
@@ -279,6 +329,10 @@ class MultiFilm(Film):
         _lib.check(self._lib.rt_multi_film_add(self._multi, int(n)))
         return self
 
+    def add_where(self, n, threshold, max_spp=None, stream_ptr=0):
+        from .errors import RtInvalid
+        raise RtInvalid("adaptive passes run on a one-device Film, not on a MultiFilm")
+
     _ready = _frame  # every read (image, noise, state, features, denoised) reports every device's status
 
     @property
@@ -317,7 +371,9 @@ HEADER_DTYPE = np.dtype([("magic", "<u4"), ("version", "<u4"), ("f32", "<i4"), (
 def unpack_state(state: np.ndarray) -> dict:
     """A saved state's parts: `header` (HEADER_DTYPE record), `sums` (rows, width, words) int64 — 3
     words per pixel in FP32 (the RGB sums in units of 2^-32), 6 in binary64 (those, then the next
-    32 bits of each) —, `flags` (rows, width) uint32 and `q` (rows, width) float64."""
+    32 bits of each) —, `flags` (rows, width) uint32 and `q` (rows, width) float64.  A non-uniform
+    film's state (layout version 2; header samples / passes: the per-pixel maxima) also has `counts`
+    (rows, width, 2) uint32, each pixel's samples and passes."""
     state = np.ascontiguousarray(state, np.uint8)
     hd = state[:HEADER_DTYPE.itemsize].view(HEADER_DTYPE)[0]
     rows, width, words = int(hd["rows"]), int(hd["width"]), 3 if hd["f32"] else 6
@@ -328,7 +384,33 @@ def unpack_state(state: np.ndarray) -> dict:
     flags = state[o:o + 4 * n].view("<u4").reshape(rows, width)
     o += 4 * n
     q = state[o:o + 8 * n].view("<f8").reshape(rows, width)
-    return dict(header=hd, sums=sums, flags=flags, q=q)
+    o += 8 * n
+    out = dict(header=hd, sums=sums, flags=flags, q=q)
+    if int(hd["version"]) >= 2:
+        out["counts"] = state[o:o + 8 * n].view("<u4").reshape(rows, width, 2)
+    return out
+
+
+def noise_from_counts(sums, q, counts) -> np.ndarray:
+    """The per-pixel relative error of a film with per-pixel counts, in numpy and binary64: the
+    operation sequence of rt_film.h rt_film_rel_error over a state's words (`unpack_state`: `sums`
+    (..., words) int64, `q` (...) float64, `counts` (..., 2) — N_p, K_p; for a uniform state
+    np.broadcast_to((samples, passes), q.shape + (2,))).  It is the value Film.noise_map shows as
+    float32 and the one Film.add_where compares: a pixel that counts is selected iff r > threshold.
+    NaN where a pixel holds no samples or fewer than two passes."""
+    sums = np.asarray(sums, np.int64)
+    q = np.asarray(q, np.float64)
+    counts = np.asarray(counts)
+    N = counts[..., 0].astype(np.float64)
+    K = counts[..., 1].astype(np.float64)
+    T = (sums[..., 0] + sums[..., 1] + sums[..., 2]).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d = q - (T * T) / N
+        v = np.where(d > 0.0, d, 0.0) / (K - 1.0)
+        se = np.sqrt(v / N) * 2.0 ** -32
+        M = T / N * 2.0 ** -32
+        r = se / np.where(M > FLOOR, M, FLOOR)
+    return np.where((counts[..., 0] > 0) & (counts[..., 1] >= 2), r, np.nan)
 
 
 def noise_from_sums(pass_sums, pass_sizes) -> dict:
@@ -360,7 +442,7 @@ def noise_from_sums(pass_sums, pass_sizes) -> dict:
 
 
 def raytrace_until(settings: CameraSettings, world, seed, noise: float, batch: int = 16, max_spp: int | None = None,
-                   denoise: bool = False, denoise_params: dict | None = None, devices=None, **kw):
+                   denoise: bool = False, denoise_params: dict | None = None, devices=None, adaptive: bool = False, **kw):
     """Render in passes of `batch` samples until the frame's noise figure (Film.noise) is at most
     `noise` (checked from the second pass on) or `max_spp` samples per pixel are reached (default
     cs_samplesPerPixel; the last pass is cut to fit).  Returns (image, info): the image is
@@ -368,11 +450,42 @@ def raytrace_until(settings: CameraSettings, world, seed, noise: float, batch: i
     converged.  denoise=True returns the denoised image instead (Film.denoised with denoise_params;
     it needs two passes: max_spp > batch) and keeps the raw one in info["raw"].  kw: Film's
     precision, device, n_shards, shard, row_block.  `devices`: a list of GPUs that render the passes
-    together (a MultiFilm; kw: precision, row_block); image and info are the one-device call's."""
+    together (a MultiFilm; kw: precision, row_block); image and info are the one-device call's.
+
+    adaptive=True: convergence is per pixel.  Two uniform passes of `batch`, then adaptive passes
+    (Film.add_where(batch, noise, max_spp)) until one selects nothing: every pixel that counts then
+    has a relative error <= noise or is within `batch` of max_spp.  Each pixel is `raytrace`'s at its
+    own count; info["spp"] is the largest count and info gains spp_mean, spp_max, selected (the
+    pixels each adaptive pass took), sample_map and rel_error (noise_from_counts of the final state; NaN
+    where a pixel does not count); converged: no pixel was stopped by max_spp.
+    Needs max_spp > batch; with denoise=True or devices= it raises RtInvalid."""
+    from .errors import RtInvalid
     if batch <= 0:
-        from .errors import RtInvalid
         raise RtInvalid("batch must be positive")
     max_spp = int(settings.cs_samplesPerPixel if max_spp is None else max_spp)
+    if adaptive:
+        if denoise or devices is not None:
+            raise RtInvalid("adaptive=True runs on one device and returns the raw image (no denoise=, no devices=)")
+        if max_spp <= batch:
+            raise RtInvalid("adaptive=True needs two uniform passes first: max_spp > batch")
+        with Film(world, settings, seed, **kw) as film:
+            film.add(batch).add(min(batch, max_spp - batch))
+            selected = []
+            while True:
+                film.add_where(batch, noise, max_spp)
+                took = film.adaptive_info()["selected"]
+                if took == 0:
+                    break
+                selected.append(took)
+            st = unpack_state(film.state())
+            r = noise_from_counts(st["sums"], st["q"], st["counts"])
+            counting = (st["flags"] == 0) & (st["counts"][..., 0] > 0)
+            ai = film.adaptive_info()
+            info = dict(spp=ai["max_samples"], passes=film.passes, noise=film.noise(),
+                        converged=not bool(np.any(r[counting] > noise)), spp_max=ai["max_samples"],
+                        spp_mean=ai["total_samples"] / max(1, int(counting.sum())), selected=selected,
+                        sample_map=st["counts"][..., 0].copy(), rel_error=np.where(counting, r, np.nan))
+            return film.image(), info
     with (Film(world, settings, seed, **kw) if devices is None else
           MultiFilm(world, settings, seed, devices=devices, **kw)) as film:
         spp, passes, figure, converged = 0, 0, None, False
