@@ -581,6 +581,45 @@ RT_FN PrimRec ld_rec64(const RT_CAS PrimRec64* p) {
 // one validity margin q (valid iff q >= 0) that also carries the interval test t > tmin as
 // t - up(tmin) >= 0 (up = next real: exact for the open interval), so the closest-hit update is
 // a single compare and select with no per-test lane-mask bookkeeping on the scalar unit.
+//
+// The validity rules of test_box and isect_plane<1> in the flat sets' loops (box groups and static
+// parallelograms tested with wave-uniform records) are decided by compares in binary64: each
+// rule is a compare of the two numbers themselves, the rules are ANDed, and q is only the verdict,
+// 0 or -1.  As margins the same rules were min(x - y, ...) >= 0: a subtraction and a minimum per
+// rule, at the binary64 rate, for a number of which only the sign was read (Cornell binary64
+// -1.4 %, profiles/valid_pred).  The two forms agree on every input without a NaN: x - y >= 0
+// exactly when x >= y (a difference of two floats is zero only for equal operands and never rounds
+// across zero; an infinite x - y has the sign the compare sees; inf - inf is a NaN, below), and
+// min(a, b) >= 0 exactly when a >= 0 and b >= 0.  t, a and b are computed as before, in the same
+// order, so every frame keeps its bits.
+// NaN: a candidate whose t, a, b or slab entry / exit is NaN is rejected, since a compare with a
+// NaN is false.  With margins fmin dropped the NaN operand and the other margins decided, so such
+// a candidate could be accepted.  A NaN arises only from a ray or record that is not finite, and
+// such a ray's radiance is not finite whatever it hits.
+// FP32 keeps the margins, instruction for instruction: its subtractions and minima run at full
+// rate, and with compares Cornell FP32 was no faster (+0.5 %; profiles/valid_pred).  Were it to
+// take the compares: FP32 flushes denormals, so x - y can flush to +-0 and pass ">= 0" where
+// x < y, but only for a difference below 2^-126, which, being a multiple of the smaller operand's
+// ulp, needs both operands below 2^-103 (~1e-31).  No rule decides a candidate on such operands:
+// one operand is the constant 1 or 1e-8, or it is tmin_up > tmin (kTmin = 1e-4 in the render
+// kernels), and a box whose tf and tn are both below 1e-31 yields a candidate that fails
+// t >= tmin_up in either form.  (A ray query may pass a tmin below 1e-31; a t below that too is
+// decided on flushed operands in either form.)
+// RT_VALID_MARGINS (compile-time, not an environment knob): -DRT_VALID_MARGINS=1 restores the
+// margins and =0 takes the compares in both precisions, for make exp, instruction-count A/B builds
+// and tests/valid_pred.  isect_sphere, isect_plane<0> and isect_plane<-1> keep their margins in
+// every build: as compares they changed the register allocation of kernels that use them (FP32
+// flat class: 6 VGPRs spilled; profiles/valid_pred) and the Cornell box tests neither.  So does
+// the BVH kernels' surface prefix (test_box<false>, test_static<.., false>): with compares four
+// binary64 BVH kernels reloaded two more spilled SGPRs inside their lane loops.  With these
+// limits every kernel but the binary64 flat ones is the margins' code, and the resource table
+// of the build (VGPRs, spills, occupancy) is unchanged in every row.
+#undef RT_MARGINS
+#ifdef RT_VALID_MARGINS
+#define RT_MARGINS RT_VALID_MARGINS
+#else
+#define RT_MARGINS (!RT_F64)
+#endif
 #if RT_F64
 RT_FN real float_up(real x) { return __builtin_bit_cast(real, __builtin_bit_cast(long long, x) + 1); }  // x > 0
 #else
@@ -605,7 +644,8 @@ RT_FN void isect_sphere(const PrimRec& r, f3 o, const RayCtx& R, real tmin, real
 // tgt_term (kQuad == 1 only; the record is the scene's redirect target, KernelParams::target_rec):
 // what target_hit and the mixture pdf make of the same numbers, t^2 / |n . d| where the ray meets
 // the parallelogram on (0, infinity) — target_hit's own conditions, without tmin and self — else 0
-template <int kQuad>
+// kCompare (kQuad == 1): the validity rules as compares where the build takes them (RT_MARGINS above)
+template <int kQuad, bool kCompare = true>
 RT_FN void isect_plane(const PrimRec& r, f3 o, const RayCtx& R, real tmin_up, bool self, real& t, real& q,
                        bool quad = false, real* tgt_term = nullptr) {
   f3 n = xyz(r.a);
@@ -614,6 +654,16 @@ RT_FN void isect_plane(const PrimRec& r, f3 o, const RayCtx& R, real tmin_up, bo
   t = dot(n, qo) * RT_RCP_NZ(denom);  // |denom| <= 1e-8 (NaN t included) fails the margin m2
   f3 prel = t * R.d - qo;
   real aa = dot(prel, xyz(r.c)), bb = dot(prel, xyz(r.e));
+  if constexpr (kQuad == 1 && kCompare && !RT_MARGINS) {
+    // the four shape compares serve the hit and the target term alike
+    const bool in = (aa >= RL(0.0)) & (bb >= RL(0.0)) & (aa <= RL(1.0)) & (bb <= RL(1.0));
+    if (tgt_term) {
+      const bool hit = (RABS(denom) > RL(1e-8)) & (t > RL(0.0)) & in;  // target_hit's own rules
+      *tgt_term = hit ? t * t * RABS(RT_RCP_NZ(denom)) : RL(0.0);  // (the reciprocal t was made with)
+    }
+    q = ((RABS(denom) >= RL(1e-8)) & (t >= tmin_up) & in & !self) ? RL(0.0) : -RL(1.0);
+    return;
+  }
   if constexpr (kQuad == 1) {
     if (tgt_term) {
       const real in = RMIN(RMIN(aa, bb), RMIN(RL(1.0) - aa, RL(1.0) - bb));
@@ -690,7 +740,7 @@ RT_FN void test_static(const PrimRec& r, const RayCtx& R, real tmin, real tmin_u
   if constexpr (kKind == RT_PRIM_CLASS_SPHERE)
     isect_sphere(r, R.o, R, tmin, tmin_up, self, t, q);
   else
-    isect_plane<kKind == RT_PRIM_CLASS_QUAD ? 1 : 0>(r, R.o, R, tmin_up, self, t, q, false, tgt_term);
+    isect_plane<kKind == RT_PRIM_CLASS_QUAD ? 1 : 0, kKeyOnly>(r, R.o, R, tmin_up, self, t, q, false, tgt_term);
   consider<kKeyOnly, kInst>(C, t, q, RT_R2I(r.c.w), pi, -1);
 }
 
@@ -780,13 +830,17 @@ RT_FN void test_box(const RT_CAS DevBox* B, const RayCtx& R, real tmin_up, Close
   const real tn = RMAX(RMAX(lo[0], lo[1]), lo[2]), tf = RMIN(RMIN(hi[0], hi[1]), hi[2]);
   const int an = lo[0] == tn ? 0 : lo[1] == tn ? 1 : 2;
   const int fn = 2 * an + (an == 0 ? flip[0] : an == 1 ? flip[1] : flip[2]);
-  const real gap = tf - tn;  // >= 0: the line meets the box
+  // flat sets: compares (RT_MARGINS above); q is then the verdict and `q >= 0` folds away
+  constexpr bool kCompare = kKeyOnly && !RT_MARGINS;
+  const real gap = tf - tn;   // margins: >= 0: the line meets the box
+  const bool met = tf >= tn;  // compares: the same
   // the entry point is nearer than the exit point: the exit matters only when the entry is not
   // a valid hit (one key compare per box)
   int ord_n, ord_f = 0, prim_n = 0, prim_f = 0;
-  const bool vn = box_face<kInst>(B, fn, RMIN(gap, tn - tmin_up), R, ord_n, prim_n, !kKeyOnly);
+  const real qn = kCompare ? ((met & (tn >= tmin_up)) ? RL(0.0) : -RL(1.0)) : RMIN(gap, tn - tmin_up);
+  const bool vn = box_face<kInst>(B, fn, qn, R, ord_n, prim_n, !kKeyOnly);
   bool vf = false;
-  const real qf = RMIN(gap, tf - tmin_up);
+  const real qf = kCompare ? ((met & (tf >= tmin_up)) ? RL(0.0) : -RL(1.0)) : RMIN(gap, tf - tmin_up);
 #if RT_BOX_EXIT_SKIP
   // ... and then only when the exit itself lies beyond tmin on a met box: rays from inside the box
   // (the Cornell room) need it, rays outside an object box (hitting its entry face, missing it, or
