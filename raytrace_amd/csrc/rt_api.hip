@@ -877,21 +877,30 @@ int adaptive_stats(const rt_film* f, CountStats& st, std::vector<uint32_t>* coun
   if (counts_out) counts_out->swap(c);
   return RT_OK;
 }
+// The argument block of a one-lane kernel (rt_lane.h: the list, feature and query kernels) for the
+// frame (cs, seed, ex): the render's, with no staged nodes (every node from memory) and a work plan
+// nothing reads (the kernels have their own).  A stack overflow sets the scene's status word `word`
+template <class R>
+int lane_params(const rt_device_scene* s, const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex, KernelParamsT<R>& P,
+                int word = 0) {
+  LaunchInputs L;
+  L.resident_lanes = 4096;
+  L.lds_nodes = 0;
+  std::string err;
+  if (int rc = rt_host_render_params(*s->host, s->variant, s->arrays<R>().rec, cs, seed, ex, L, P, err))
+    return fail(rc, "%s", err.c_str());
+  P.status = s->status + word;
+  return RT_OK;
+}
 // one adaptive pass of precision R on st: select, the zeroed workspace, the list kernel, the merge
 template <class R>
 int adaptive_pass(rt_film* f, int n_samples, double threshold, long long max_samples, hipStream_t st) {
   const rt_device_scene* s = f->scene;
   if (int rc = ensure_precision<R>(s)) return rc;
-  LaunchInputs L;
-  L.resident_lanes = 4096;  // (the work plan is the render's; the list kernel has its own)
-  L.lds_nodes = 0;          // no staged nodes: every node from memory
   rt_camera_settings cs = f->cs;
   cs.samples_per_pixel = n_samples;
   KernelParamsT<R> P;
-  std::string err;
-  if (int rc = rt_host_render_params(*s->host, s->variant, s->arrays<R>().rec, &cs, f->seed, &f->ex, L, P, err))
-    return fail(rc, "%s", err.c_str());
-  P.status = s->status;
+  if (int rc = lane_params(s, &cs, f->seed, &f->ex, P)) return rc;
   P.accum = (unsigned long long*)f->ws;
   P.nanflag = (unsigned int*)(f->ws + f->ws_lay.off_flag);
   P.counter = (int*)(f->ws + f->ws_lay.off_ctr);
@@ -960,16 +969,10 @@ template <class R>
 int film_features(rt_film* f, unsigned long long* feat, int n_feat, hipStream_t st) {
   const rt_device_scene* s = f->scene;
   if (int rc = ensure_precision<R>(s)) return rc;
-  LaunchInputs L;
-  L.resident_lanes = 4096;  // (the work plan is the render's; the feature kernel has its own)
-  L.lds_nodes = 0;          // no staged nodes: every node from memory
   rt_camera_settings cs = f->cs;
   cs.samples_per_pixel = n_feat;
   KernelParamsT<R> P;
-  std::string err;
-  if (int rc = rt_host_render_params(*s->host, s->variant, s->arrays<R>().rec, &cs, f->seed, &f->ex, L, P, err))
-    return fail(rc, "%s", err.c_str());
-  P.status = s->status;
+  if (int rc = lane_params(s, &cs, f->seed, &f->ex, P)) return rc;
   HIP_TRY(hipMemsetAsync(feat, 0, f->n_pixels * rt_feat_words(!f->f32) * sizeof(long long), st));
   if (rt_launch_features(P, s->variant, feat, n_feat, st))
     return fail(RT_E_HIP, "feature launch failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1004,14 +1007,8 @@ int cast_enqueue(const rt_device_scene* s, const rt_ray* d_rays, rt_hit* d_hits,
   ex.device = s->device;
   ex.n_shards = 1;
   ex.row_block = 4;
-  LaunchInputs L;
-  L.resident_lanes = 4096;  // (the work plan is the render's; the query kernel has none)
-  L.lds_nodes = 0;          // no staged nodes: every node from memory
   KernelParamsT<R> P;
-  std::string err;
-  if (int rc = rt_host_render_params(*s->host, s->variant, s->arrays<R>().rec, &cs, 0, &ex, L, P, err))
-    return fail(rc, "%s", err.c_str());
-  P.status = s->status + word;
+  if (int rc = lane_params(s, &cs, 0, &ex, P, word)) return rc;
   // (experiments and tests: fewer stack rows than the scene's BVH needs, the defined overflow path)
   if (const char* e = rt_knob("RT_AMD_CAST_STACK")) P.stack_depth = std::max(1, std::min(P.stack_depth, atoi(e)));
   HIP_TRY(hipSetDevice(s->device));

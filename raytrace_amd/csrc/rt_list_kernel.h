@@ -1,6 +1,6 @@
 // rt_list_kernel.h — the pixel-list kernel and its launcher for ONE precision: included by
 // rt_list.hip (RT_F64 0) and rt_list64_nl.hip (RT_F64 1), each its own translation unit.  The per-lane
-// logic is rt_list.h over rt_trace.h's functions; the render kernels' translation units do not see
+// logic is rt_list.h over rt_lane.h and rt_trace.h's functions; the render kernels' translation units do not see
 // this file and the spill gate does not count this kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,8 +11,6 @@
 #include "rt_list.h"
 
 namespace RT_NS {
-
-constexpr int kListBlock = 64;  // one wave: nothing is shared across a workgroup but the claimed id
 
 // An adaptive pass's samples (rt_adaptive.h): list entry e = {tile pixel, N_p} of the *n_list entries
 // the select kernel wrote receives samples [N_p, N_p + n_samples) in chunks: item id = e x n_chunks +
@@ -26,11 +24,10 @@ constexpr int kListBlock = 64;  // one wave: nothing is shared across a workgrou
 // sample chunks up to a selection of 131 072 pixels at 16 samples, chunks of 4 at 360 000 — the
 // fastest of the chunks measured at both, profiles/adaptive).  A lane sums its chunk in an Acc and
 // adds the nonzero words to the pass workspace (P.accum, P.nanflag) at its tile pixel with 64-bit
-// integer atomics: the sums do not depend on the chunking or the schedule.  BVH classes: the lane's
-// traversal stack is [stack_depth + 1][64] ints of dynamic LDS, no staged nodes (lds_nodes = 0).
+// integer atomics: the sums do not depend on the chunking or the schedule.  Block and stack: rt_lane.h.
 // The kernel's first argument is its KernelParams (rt_trace.h RT_KARGS).
 template <int kVar, int kTex, int kMedia, bool kMats, bool kInst, int kLeaf>
-__global__ __launch_bounds__(kListBlock) void rt_list_kernel(KernelParams P, const rt_adaptive_rec* __restrict__ list,
+__global__ __launch_bounds__(kLaneBlock) void rt_list_kernel(KernelParams P, const rt_adaptive_rec* __restrict__ list,
                                                              const int* __restrict__ n_list, int n_samples, int chunk_arg,
                                                              int fill_lanes) {
   extern __shared__ int smem[];
@@ -44,11 +41,11 @@ __global__ __launch_bounds__(kListBlock) void rt_list_kernel(KernelParams P, con
   chunk = min(chunk, n_samples);
   const int n_chunks = (n_samples + chunk - 1) / chunk;
   const long long n_items = (long long)count * n_chunks;
-  const Trav W{smem + threadIdx.x, kListBlock, nullptr};
+  const Trav W{smem + threadIdx.x, kLaneBlock, nullptr};
   int overflow = 0;
   for (;;) {
     int base = 0;
-    if (threadIdx.x == 0) base = atomicAdd(P.counter, kListBlock);
+    if (threadIdx.x == 0) base = atomicAdd(P.counter, kLaneBlock);
     base = __builtin_amdgcn_readfirstlane(base);
     // wave-uniform exit (a cursor past 2^31 never happens: the launcher bounds the ids); the claim
     // above is reached by the whole wave, the lanes' work below rejoins before the next one
@@ -103,14 +100,13 @@ int rt_launch_list(const KernelParamsT<RT_NS::real>& p, int variant, const rt_ad
   if (!fn) return -1;
   // the ids a wave claims stay below 2^31: worst case every tile pixel with one-sample chunks, plus
   // one claim per wave of the grid behind the end
-  const int resident = 131072;          // 256 CUs x 8 waves x 64 lanes: the grid
+  const int resident = kLaneResident;    // the grid
   const int fill_lanes = 16 * resident;  // items to aim for: short chunks even out the lanes' path lengths
-  const long long worst = (pixels * n_samples + kListBlock - 1) / kListBlock;
-  const long long blocks = std::min<long long>(worst, resident / kListBlock);
-  if (pixels * n_samples + (blocks + 1) * kListBlock > 0x7fffffffLL) return -1;
-  const KernelClass c = rt_class_of(RT_F64, variant);
-  const size_t lds = c.var == RT_VAR_FLAT ? 0 : (size_t)(p.stack_depth + 1) * kListBlock * sizeof(int);
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kListBlock), lds, (hipStream_t)stream, p, list, n_list, n_samples, chunk,
+  const long long worst = (pixels * n_samples + kLaneBlock - 1) / kLaneBlock;
+  const long long blocks = std::min<long long>(worst, resident / kLaneBlock);
+  if (pixels * n_samples + (blocks + 1) * kLaneBlock > 0x7fffffffLL) return -1;
+  const size_t lds = lane_stack_bytes(variant, p.stack_depth);
+  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kLaneBlock), lds, (hipStream_t)stream, p, list, n_list, n_samples, chunk,
                      fill_lanes);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -1,17 +1,18 @@
 // rt_query.h — one ray query of ONE precision (include/rt.h rt_scene_cast): included after rt_trace.h
-// of the same RT_F64 (no include guard, as rt_trace.h's per-precision part), by rt_query.hip /
-// rt_query64.hip / rt_query64_nl.hip for the device and by tests/query_emu for the host (RT_HOST_EMU).
+// of the same RT_F64, includes rt_lane.h itself (no include guard, as rt_trace.h's per-precision
+// part), by rt_query.hip / rt_query64.hip / rt_query64_bvh.hip for the device and by tests/query_emu
+// for the host (RT_HOST_EMU).
 //
-// query_ray turns one rt_ray into one rt_hit against the scene's surface set, as segment 0 of a
-// render queries it (rt_features.h feature_sample's `query`): the flat sets through closest<true>,
-// otherwise the surface prefix and trav_round with the class's instancing and leaf flags.  What
-// differs from a camera ray: the ray is the caller's (normalised in binary64 before it is converted
-// to the kernel's precision), its time word is floor(time 2^24) << 8 (u01 of it is the time the
+// query_ray turns one rt_ray into one rt_hit against the scene's surface set, by the query a
+// render's segment runs (rt_lane.h lane_query, with its any-hit stop) and the render's hit
+// information (rt_trace.h surface_info_world).  What differs from a camera ray: the ray is the
+// caller's (normalised in binary64 before it is converted to the kernel's precision), its time word is floor(time 2^24) << 8 (u01 of it is the time the
 // kernel sees, rt_trace.h u01), tmin stands where kTmin does, and tmax enters as the initial Closest
 // ({tmax, 0, -1, -1}; FP32: the key hit_key(tmax, 0)), so a candidate needs t < tmax strictly — no
 // leaf's key order is below 0.  self_gid / self_inst are -1: a query ray leaves no leaf.  Media are
 // not queried (their events are random draws keyed by pixel and sample).
 #include "../../include/rt.h"
+#include "rt_lane.h"  // (per precision, like this file: no include guard, included by exactly one body header)
 
 namespace RT_NS {
 
@@ -47,17 +48,11 @@ RT_FN void query_ray(const KernelParams& P0, const real* prims_, const int* prim
   const double dx = q.dir[0] / m, dy = q.dir[1] / m, dz = q.dir[2] / m;
   const double il = 1.0 / sqrt(dx * dx + dy * dy + dz * dz);
   RayCtx R;
+  ray_clear(R);
   R.o = mk3((real)q.origin[0], (real)q.origin[1], (real)q.origin[2]);
   R.d = mk3((real)(dx * il), (real)(dy * il), (real)(dz * il));
-#if RT_NODE_F32
-  R.idir = R.off0 = R.off1 = f3n{0.f, 0.f, 0.f};
-#else
-  R.idir = R.oidir = mk3(RL(0.), RL(0.), RL(0.));
-#endif
   const double tw = floor(q.time * 16777216.0);
   R.time_w = (uint32_t)(tw > 16777215.0 ? 16777215.0 : tw) << 8;
-  R.self_gid = -1;
-  R.self_inst = -1;
   const real tmin = (real)q.tmin, tmax = (real)q.tmax;
   Closest C = no_hit();
   C.t = tmax;
@@ -65,29 +60,17 @@ RT_FN void query_ray(const KernelParams& P0, const real* prims_, const int* prim
   const unsigned long long key0 = hit_key(tmax, 0);
   C.key = key0;
 #endif
-  bool hit;
-  {
-    // (the kernel arguments re-read, as the render's lane loops do: rt_trace.h RT_KARGS)
-    const KernelParams& P = RT_KARGS(P0);
-    if constexpr (kFlat) {
-      closest<true>(P, prims, P.surface_root, 0, R, tmin, C, W, &overflow);
+  if constexpr (!kFlat) prep_ray(R);
+  // any-hit: a BVH traversal ends at the first accepted hit
+  lane_query<kVar, kInst, kLeaf>(P0, prims, W, R, RT_KARGS(P0).surface_root, 0, tmin, C, overflow, any);
+  bool hit = C.prim >= 0;
+  if constexpr (kFlat) {
 #if RT_F64
-      hit = C.t < tmax;  // every accepted candidate is below tmax
-      C.prim = C.ord;    // slot = primitive index (rt_trace.h closest_flat)
+    hit = C.t < tmax;  // every accepted candidate is below tmax
+    C.prim = C.ord;    // slot = primitive index (rt_trace.h closest_flat)
 #else
-      hit = C.key < key0;
+    hit = C.key < key0;
 #endif
-    } else {
-      prep_ray(R);
-      TravState S;
-      trav_begin(S, P.surface_root, tmin);
-      S.C = C;
-      prefix_hits<kInst>(P, prims, R, tmin, S.C);
-      // any-hit: the traversal ends at the first accepted hit
-      while (!trav_done(S) && !(any && S.C.prim >= 0)) trav_round<kInst, kLeaf>(P, R, S, W, overflow RT_PROF_NULLARG);
-      C = S.C;
-      hit = C.prim >= 0;
-    }
   }
   if (!hit) {
     H.t = __builtin_huge_val();
@@ -106,23 +89,13 @@ RT_FN void query_ray(const KernelParams& P0, const real* prims_, const int* prim
   H.instance = best_inst;
   int mat = ldci(prim_mat, best);
   const bool need_uv = (flags & RT_QUERY_UV) != 0;
-  HitInfo h;
-  bool in_object = false;
   if constexpr (kInst) {
-    if (best_inst >= 0) {  // hit information in object space, point and normal back to world (rt_features.h)
-      const RT_CAS DevInstance* I = inst_rec(P, best_inst);
-      const int im = I->material;
+    if (best_inst >= 0) {  // a placement's own material overrides its leaves' (rt_trace.h hit_material)
+      const int im = inst_rec(P, best_inst)->material;
       if (im >= 0) mat = im;
-      RayCtx Ro = R;
-      Ro.o = inst_to_object(I, R.o, true);
-      Ro.d = inst_to_object(I, R.d, false);
-      h = surface_info(P, prims, best, Ro, C.t, need_uv);
-      h.p = R.o + C.t * R.d;
-      h.n = inst_rotate(I, h.n);
-      in_object = true;
     }
   }
-  if (!in_object) h = surface_info(P, prims, best, R, C.t, need_uv);
+  HitInfo h = surface_info_world<kInst>(P, prims, best, best_inst, R, C.t, need_uv);
   // a sphere's (p - c) / r is unit up to the hit point's rounding over r (eps |p| / r, many eps for
   // a small sphere far from the origin): the record's normal is re-normalised
   h.n = unit(h.n);

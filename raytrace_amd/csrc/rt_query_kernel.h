@@ -1,7 +1,7 @@
 // rt_query_kernel.h — the ray-query kernel (include/rt.h rt_scene_cast) and its launcher for ONE
 // precision: included by rt_query.hip (RT_F64 0: every class), rt_query64.hip (RT_F64 1: the flat
 // class and the launcher) and rt_query64_bvh.hip (RT_F64 1: the BVH classes), each its own
-// translation unit.  The per-lane logic is rt_query.h over rt_trace.h's closest-hit code; the render
+// translation unit.  The per-lane logic is rt_query.h over rt_lane.h and rt_trace.h's closest-hit code; the render
 // and feature kernels' translation units do not see this file.
 //   RT_QUERY_PART 0: every class and the launcher; 1: the flat class and the launcher; 2: the BVH classes
 #include <hip/hip_runtime.h>
@@ -17,8 +17,6 @@
 
 namespace RT_NS {
 
-constexpr int kQueryBlock = 64;  // one wave: nothing is shared across a workgroup
-
 // the records move as 16-byte vectors: a wave's 64 rays are 5 KB contiguous, its hits 6 KB
 struct alignas(16) q16 {
   double x, y;
@@ -29,21 +27,19 @@ __device__ __forceinline__ double q_ints(int lo, int hi) {
 }
 
 // One lane per ray, in the caller's order: lane id traces rays[id] into hits[id].  Rays are neither
-// sorted nor compacted — the caller's coherence is the kernel's.  BVH classes: the lane's traversal
-// stack is [stack_depth + 1][64] ints of dynamic LDS, as the render kernels lay it out; no nodes are
-// staged (the host passes lds_nodes = 0).  The kernel's first argument is its KernelParams, as the
-// render kernels' (rt_trace.h RT_KARGS).
+// sorted nor compacted — the caller's coherence is the kernel's.  Block and stack: rt_lane.h.  The
+// kernel's first argument is its KernelParams, as the render kernels' (rt_trace.h RT_KARGS).
 template <int kVar, bool kInst, int kLeaf>
-__global__ __launch_bounds__(kQueryBlock) void rt_query_kernel(KernelParams P, const rt_ray* __restrict__ rays,
+__global__ __launch_bounds__(kLaneBlock) void rt_query_kernel(KernelParams P, const rt_ray* __restrict__ rays,
                                                                rt_hit* __restrict__ hits, const int* __restrict__ prim_mat,
                                                                long long n, int flags) {
   extern __shared__ int smem[];
-  const long long id = (long long)blockIdx.x * kQueryBlock + threadIdx.x;
+  const long long id = (long long)blockIdx.x * kLaneBlock + threadIdx.x;
   if (id >= n) return;
   const q16* rp = reinterpret_cast<const q16*>(rays + id);
   const q16 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3], r4 = rp[4];
   const rt_ray q{{r0.x, r0.y, r1.x}, {r1.y, r2.x, r2.y}, r3.x, r3.y, r4.x, 0.0};
-  const Trav W{smem + threadIdx.x, kQueryBlock, nullptr};
+  const Trav W{smem + threadIdx.x, kLaneBlock, nullptr};
   rt_hit H;
   int overflow = 0;
   query_ray<kVar, kInst, kLeaf>(P, P.prims, prim_mat, W, q, flags, H, overflow);
@@ -98,10 +94,10 @@ int rt_launch_query(const KernelParamsT<RT_NS::real>& p, int variant, const rt_r
   else fn = query_kernel_of_class<false>(c);
 #endif
   if (!fn) return -1;
-  const long long blocks = (n + kQueryBlock - 1) / kQueryBlock;
+  const long long blocks = (n + kLaneBlock - 1) / kLaneBlock;
   if (blocks > 0x7fffffffLL) return -1;
-  const size_t lds = c.var == RT_VAR_FLAT ? 0 : (size_t)(p.stack_depth + 1) * kQueryBlock * sizeof(int);
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kQueryBlock), lds, (hipStream_t)stream, p, rays, hits, prim_mat, n,
+  const size_t lds = lane_stack_bytes(variant, p.stack_depth);
+  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kLaneBlock), lds, (hipStream_t)stream, p, rays, hits, prim_mat, n,
                      flags);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -429,6 +429,18 @@ struct RayCtx {
   int self_gid;   // the leaf the ray leaves (skipped: FP32 robustness, rt_trace.h isect_*)
   int self_inst;  // ... and its instance (-1: a world leaf; two-level instancing, RT_VAR_INST)
 };
+// The ray a lane holds before its first camera ray: every field defined (zero, no leaf left)
+RT_FN void ray_clear(RayCtx& R) {
+  R.o = R.d = mk3(RL(0.), RL(0.), RL(0.));
+#if RT_NODE_F32
+  R.idir = R.off0 = R.off1 = f3n{0.f, 0.f, 0.f};
+#else
+  R.idir = R.oidir = R.o;
+#endif
+  R.time_w = 0u;
+  R.self_gid = -1;
+  R.self_inst = -1;
+}
 // The leaf the ray leaves: gid equal, and (instancing) the same placement of the object.
 template <bool kInst>
 RT_FN bool is_self(const RayCtx& R, int gid, int cur_inst) {
@@ -1052,18 +1064,23 @@ struct Acc {
   long long hi[3];
   unsigned long long lo[3];
 };
-RT_FN void acc_add(Acc& A, int c, real x, bool& bad) {
-  if (!(RABS(x) < RL(1.0e9))) {
-    bad = true;
-    return;
-  }
+// hi, lo += the two words of x, |x| < 1e9 (the sums of the render, acc_add, and of the first-hit
+// features, rt_features.h feat_add)
+RT_FN void fixed_words_add(real x, long long& hi, unsigned long long& lo) {
   // (the same words from 32-bit conversions only, floor(x) 2^32 + floor(frac(x) 2^32), measured no
   // faster: Cornell 4.887 vs 4.889 ms, pawn+fog +1 %; profiles/r5/variants.  From the low words of
   // integer-valued binary64 plus 1.5 2^52, no conversions: Cornell +1.4 %, profiles/r6/flat)
   const real xs = x * RL(4294967296.0);
   const real fl = RFLOOR(xs);
-  A.hi[c] += (long long)fl;
-  A.lo[c] += (unsigned long long)(unsigned)((xs - fl) * RL(4294967296.0));
+  hi += (long long)fl;
+  lo += (unsigned long long)(unsigned)((xs - fl) * RL(4294967296.0));
+}
+RT_FN void acc_add(Acc& A, int c, real x, bool& bad) {
+  if (!(RABS(x) < RL(1.0e9))) {
+    bad = true;
+    return;
+  }
+  fixed_words_add(x, A.hi[c], A.lo[c]);
 }
 #else
 // trunc(x 2^32) (RT_ACC_WORDS = 3)
@@ -1555,6 +1572,39 @@ RT_FN void medium_event(const KernelParams& P, int m, uint32_t pix, int sample, 
                         real& tbest, int& hit_medium) {
   medium_draw(P, m, medium_block(P, m, pix, sample, seg), lo, hi, tbest, hit_medium);
 }
+// constantMedium (Geometry.hs:306-328) as a chain of queries after the segment's surface hit C: per
+// medium its first boundary hit and, for a ray that enters it before the closest hit so far, the
+// exit hit, then the free-flight draw over that interval.  query(root, set, tmin, C1) runs one
+// closest-hit query over the medium's boundary set.
+template <class Query>
+RT_FN void media_chain(const KernelParams& P, cfp prims, const RayCtx& R, uint32_t pix, int sample, int seg,
+                       const Closest& C, real& tbest, int& hit_medium, Query query) {
+  for (int m = 0; m < P.n_media; ++m) {
+    const DevMedium& M = P.media[m];
+    Closest C1 = no_hit();
+    if (M.alias_surface) {  // the boundary is the surface set: its first hit is the surface hit
+      C1.t = C.t;
+      C1.prim = C.prim;
+    } else {
+      query(M.root, m + 1, kTmin, C1);
+    }
+    if (C1.prim < 0) continue;
+    const real t1 = C1.t;
+    real lo, hi;
+    if (prim_front(P, prims, C1.prim, R, t1)) {
+      if (!(t1 < tbest)) continue;
+      Closest C2 = no_hit();
+      query(M.root, m + 1, t1, C2);
+      if (C2.prim < 0) continue;
+      lo = t1;
+      hi = C2.t;
+    } else {
+      lo = kTmin;
+      hi = t1;
+    }
+    medium_event(P, m, pix, sample, seg, lo, hi, tbest, hit_medium);
+  }
+}
 
 // The HemisphereF / SphereF scatter (Ray.hs:187-224): the direction from the redirect mixture
 // (target k by the cumulative probabilities, else the default sampler) and the weight
@@ -1674,6 +1724,48 @@ RT_FN bool mixture_scatter(const KernelParams& P, const HitInfo& h, const RayCtx
   return !(hemi && pdf1 <= RL(0.0));
 }
 
+// cs_background of a ray of direction d that hits nothing (Ray.hs:179)
+RT_FN f3 background(const KernelParams& P, f3 d) {
+  f3 bg = ld3(P.cam.bg0);
+  if (P.cam.bg_kind == 1) {
+    real a = RL(0.5) * (d.y + RL(1.0));
+    bg = (RL(1.0) - a) * bg + a * ld3(P.cam.bg1);
+  }
+  return bg;
+}
+// The material record of a hit (DevMaterial: the medium's phase material, or the primitive's own)
+template <bool kInst>
+RT_FN const RT_CAS DevMaterial* hit_material(const KernelParams& P, int best, int best_inst, int hit_medium) {
+  const RT_CAS DevMaterial* Mp = hit_medium >= 0
+                                     ? (const RT_CAS DevMaterial*)P.mats + P.media[hit_medium].material
+                                     : (const RT_CAS DevMaterial*)P.prim_shade + best;
+  if constexpr (kInst) {  // a placement's own material (the outermost `<$`) overrides its leaves'
+    if (hit_medium < 0 && best_inst >= 0) {
+      const int im = inst_rec(P, best_inst)->material;
+      if (im >= 0) Mp = (const RT_CAS DevMaterial*)P.mats + im;
+    }
+  }
+  return Mp;
+}
+// surface_info of the hit at t of primitive `best`, through its placement where it has one
+template <bool kInst>
+RT_FN HitInfo surface_info_world(const KernelParams& P, cfp prims, int best, int best_inst, const RayCtx& R, real t,
+                                 bool need_uv) {
+  if constexpr (kInst) {
+    if (best_inst >= 0) {  // hit information in object space, point and normal back to world
+      const RT_CAS DevInstance* I = inst_rec(P, best_inst);
+      RayCtx Ro = R;
+      Ro.o = inst_to_object(I, R.o, true);
+      Ro.d = inst_to_object(I, R.d, false);
+      HitInfo h = surface_info(P, prims, best, Ro, t, need_uv);
+      h.p = R.o + t * R.d;
+      h.n = inst_rotate(I, h.n);
+      return h;
+    }
+  }
+  return surface_info(P, prims, best, R, t, need_uv);
+}
+
 // One rayColor level after the closest hit (Ray.hs:176-224): background on a miss, else the
 // material of the surface / medium hit.  Updates L, T and, when the path continues, the ray
 // (and seg).  Returns true when the path terminates.
@@ -1686,11 +1778,7 @@ RT_FN bool shade_event(const KernelParams& P, cfp prims, uint32_t pix, int sampl
   RT_HOOK_SEGMENT(pix, sample, seg, R, tbest, best, hit_medium, L, T);
   if (hit_medium < 0 && best < 0) {
     // miss: cs_background (Ray.hs:179)
-    f3 bg = ld3(P.cam.bg0);
-    if (P.cam.bg_kind == 1) {
-      real a = RL(0.5) * (R.d.y + RL(1.0));
-      bg = (RL(1.0) - a) * bg + a * ld3(P.cam.bg1);
-    }
+    f3 bg = background(P, R.d);
     L = L + T * bg;
 #ifndef RT_HOST_EMU
     Tf = bg;  // (defined, in a register already; the path ends)
@@ -1699,15 +1787,7 @@ RT_FN bool shade_event(const KernelParams& P, cfp prims, uint32_t pix, int sampl
   }
   bool terminate = false;
   // the material: one record load (DevMaterial, per primitive for surfaces)
-  const RT_CAS DevMaterial* Mp = hit_medium >= 0
-                                     ? (const RT_CAS DevMaterial*)P.mats + P.media[hit_medium].material
-                                     : (const RT_CAS DevMaterial*)P.prim_shade + best;
-  if constexpr (kInst) {  // a placement's own material (the outermost `<$`) overrides its leaves'
-    if (hit_medium < 0 && best_inst >= 0) {
-      const int im = inst_rec(P, best_inst)->material;
-      if (im >= 0) Mp = (const RT_CAS DevMaterial*)P.mats + im;
-    }
-  }
+  const RT_CAS DevMaterial* Mp = hit_material<kInst>(P, best, best_inst, hit_medium);
   const DevMaterial Mt = DevMaterial{Mp->kind, Mp->tex, Mp->param, Mp->tex_const, {RL(0.), RL(0.), RL(0.)}, RL(0.)};
   // every material but pitchBlack and dielectric reads its texture; constant textures come with
   // the record, the others are evaluated once (one inlined copy keeps the register allocation down)
@@ -1723,6 +1803,7 @@ RT_FN bool shade_event(const KernelParams& P, cfp prims, uint32_t pix, int sampl
     h.v = RL(0.);
     h.gid = -1;
   } else {
+    // (surface_info_world, in the render kernels' own text: calling it reorders the BVH kernels' code)
     if constexpr (kInst) {
       if (best_inst >= 0) {  // hit information in object space, point and normal back to world
         const RT_CAS DevInstance* I = inst_rec(P, best_inst);
@@ -1870,6 +1951,17 @@ struct ItemCtx {
   uint32_t pix;   // global pixel gy * width + px
   uint32_t pxgy;  // gy << 16 | px (rt_build.cpp limits images to 65535 x 65535)
 };
+// Tile pixel tp -> its image row gy under the shard row interleave (rt_exec: blocks of row_block
+// rows dealt to the shards in turn), the global pixel gy * width + px and gy << 16 | px
+RT_FN void tile_pixel(const KernelParams& P, int tp, int& gy, uint32_t& pix, uint32_t& pxgy) {
+  const int W = P.cam.width;
+  const int tr = (int)fast_div((uint32_t)tp, P.div_width);
+  const int px = tp - tr * W;
+  const int tb = (int)fast_div((uint32_t)tr, P.div_block);
+  gy = (tb * P.n_shards + P.shard) * P.row_block + (tr - tb * P.row_block);
+  pix = (uint32_t)(gy * W + px);
+  pxgy = (uint32_t)gy << 16 | (uint32_t)px;
+}
 // kTwoSizes: the item may be big (flat kernel only: the BVH kernels run one item size, rt_build.cpp
 // rt_host_plan_work, so their register allocation does not carry the decode)
 template <bool kTwoSizes>
@@ -1882,6 +1974,7 @@ RT_FN bool open_item(const KernelParams& P, int item, ItemCtx& I) {
   const int n = big ? P.n_big_chunks : P.n_chunks;
   I.tp = (int)fast_div((uint32_t)id, big ? P.div_big : P.div_small);
   const int k = id - I.tp * n;
+  // (tile_pixel's decode, in the render kernels' own text: calling it reorders their scalar loads)
   const int tr = (int)fast_div((uint32_t)I.tp, P.div_width);
   const int px = I.tp - tr * W;
   const int tb = (int)fast_div((uint32_t)tr, P.div_block);
@@ -1991,6 +2084,7 @@ RT_FN int lane_loop_lockstep(const KernelParams& P0, Work& work, const Trav& TW,
   // the ray of a path that ended: NaN in the host emulator)
   constexpr bool kDefer = kFlat && !kMedia && !kMats;
   real apdf = RL(1.);
+  // (ray_clear, in this loop's own text: calling it reorders the FP32 flat kernels' code)
   RayCtx R;
   R.o = R.d = mk3(RL(0.), RL(0.), RL(0.));
 #if RT_NODE_F32
@@ -2057,6 +2151,7 @@ RT_FN int lane_loop_lockstep(const KernelParams& P0, Work& work, const Trav& TW,
     const int best = C.prim;
     int hit_medium = -1;
     // media: compiled only into the instantiations for scenes that have them (kMedia)
+    // (media_chain over closest<kFlat>, in this loop's own text: calling it reorders the flat media kernels' code)
     const int n_media = kMedia ? P.n_media : 0;
     for (int m = 0; m < n_media; ++m) {
       // constantMedium (Geometry.hs:306-328)
@@ -2171,15 +2266,7 @@ RT_FN void lane_loop_flat_ring(const KernelParams& P0, Work& work, real* ring_od
   f3 T = mk3(RL(1.), RL(1.), RL(1.));
   real apdf = RL(1.);
   RayCtx R;
-  R.o = R.d = mk3(RL(0.), RL(0.), RL(0.));
-#if RT_NODE_F32
-  R.idir = R.off0 = R.off1 = f3n{0.f, 0.f, 0.f};
-#else
-  R.idir = R.oidir = R.o;
-#endif
-  R.time_w = 0u;
-  R.self_gid = -1;
-  R.self_inst = -1;
+  ray_clear(R);
   RT_PROF_DECL
   for (;;) {
     const KernelParams& P = RT_KARGS(P0);  // (per iteration: RT_KARGS)
@@ -2345,15 +2432,7 @@ RT_FN int lane_loop_bvh(const KernelParams& P0, Work& work, const Trav& TW, cons
   // Ray.hs:179), so a sample's radiance is that one term, formed in `shade` and summed at once.
   f3 T = mk3(RL(1.), RL(1.), RL(1.));
   RayCtx R;
-  R.o = R.d = mk3(RL(0.), RL(0.), RL(0.));
-#if RT_NODE_F32
-  R.idir = R.off0 = R.off1 = f3n{0.f, 0.f, 0.f};
-#else
-  R.idir = R.oidir = R.o;
-#endif
-  R.time_w = 0u;
-  R.self_gid = -1;
-  R.self_inst = -1;
+  ray_clear(R);
   TravState S;
   trav_begin(S, RT_EMPTY_ROOT, kTmin);
   // query sequencing within a segment (the chain, kMedia 1): q = 0 surfaces; q = 1 + 2m / 2 + 2m
