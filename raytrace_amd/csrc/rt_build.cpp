@@ -1196,6 +1196,89 @@ int rt_host_match_target(const HostScene& H, int variant, KernelParamsT<R>& P) {
   return 0;
 }
 
+// Screen rectangles for the camera segments (KernelParams::cull_box / cull_quad; rt_trace.h
+// closest_flat_primary).  A pinhole camera's rays leave cam.center towards top_left + a pixel_u +
+// b pixel_v with (a, b) in the pixel's footprint [px, px + 1) x [gy, gy + 1).  A point X strictly in
+// front of the camera, X - center = c (top_left - center + a pixel_u + b pixel_v) with c > 0, is
+// met only by the ray through (a, b); a convex record whose corners are all in front projects into
+// the convex hull of its corners' (a, b).  The rectangle is their bounding rectangle in whole
+// pixels, padded by one pixel on every side (the projection's and the tests' rounding, edge
+// pixels).  Everything in binary64 from the records and camera fields the kernel reads.
+namespace {
+constexpr uint32_t kCullAllLo = 0u, kCullAllHi = 0xffffffffu;
+// rows m[0..2] times x = b (Cramer); false: singular
+bool solve3(const d3* m, d3 b, d3& x) {
+  const double det = dot(m[0], cross(m[1], m[2]));
+  if (!(std::fabs(det) > 0) || !std::isfinite(det)) return false;
+  const d3 c0 = cross(m[1], m[2]), c1 = cross(m[2], m[0]), c2 = cross(m[0], m[1]);
+  x = divs(smul(b.x, c0) + smul(b.y, c1) + smul(b.z, c2), det);
+  return std::isfinite(x.x) && std::isfinite(x.y) && std::isfinite(x.z);
+}
+template <class R>
+void cull_rect(const KernelParamsT<R>& P, const d3* corners, int n, uint32_t* out) {
+  out[0] = kCullAllLo, out[1] = kCullAllHi;
+  const d3 center = {(double)P.cam.center[0], (double)P.cam.center[1], (double)P.cam.center[2]};
+  const d3 pu = {(double)P.cam.pixel_u[0], (double)P.cam.pixel_u[1], (double)P.cam.pixel_u[2]};
+  const d3 pv = {(double)P.cam.pixel_v[0], (double)P.cam.pixel_v[1], (double)P.cam.pixel_v[2]};
+  const d3 w0 = d3{(double)P.cam.top_left[0], (double)P.cam.top_left[1], (double)P.cam.top_left[2]} - center;
+  // X - center = a' pu + b' pv + c' w0: the matrix with those columns, as rows of its transpose
+  const d3 rows[3] = {{pu.x, pv.x, w0.x}, {pu.y, pv.y, w0.y}, {pu.z, pv.z, w0.z}};
+  double a0 = INFINITY, a1 = -INFINITY, b0 = INFINITY, b1 = -INFINITY;
+  for (int i = 0; i < n; ++i) {
+    d3 s;
+    if (!solve3(rows, corners[i] - center, s)) return;
+    if (!(s.z > 1e-9)) return;  // not strictly in front of the camera
+    const double a = s.x / s.z, b = s.y / s.z;
+    if (!std::isfinite(a) || !std::isfinite(b)) return;
+    a0 = std::min(a0, a), a1 = std::max(a1, a), b0 = std::min(b0, b), b1 = std::max(b1, b);
+  }
+  const double x0 = std::floor(a0) - 1, x1 = std::floor(a1) + 1, y0 = std::floor(b0) - 1, y1 = std::floor(b1) + 1;
+  if (x1 < 0 || y1 < 0 || x0 > 65535 || y0 > 65535) {  // off the frame: no pixel (lo > hi)
+    out[0] = 1u, out[1] = 0u;
+    return;
+  }
+  const uint32_t px0 = (uint32_t)std::max(0.0, x0), px1 = (uint32_t)std::min(65535.0, x1);
+  const uint32_t gy0 = (uint32_t)std::max(0.0, y0), gy1 = (uint32_t)std::min(65535.0, y1);
+  out[0] = gy0 << 16 | px0;
+  out[1] = gy1 << 16 | px1;
+}
+}  // namespace
+template <class R>
+void rt_host_cull_rects(const HostScene& H, KernelParamsT<R>& P) {
+  for (int j = 0; j < RT_CULL_BOXES; ++j) P.cull_box[j][0] = kCullAllLo, P.cull_box[j][1] = kCullAllHi;
+  for (int j = 0; j < RT_CULL_QUADS; ++j) P.cull_quad[j][0] = kCullAllLo, P.cull_quad[j][1] = kCullAllHi;
+  if (!H.flat || P.cam_defocus) return;
+  if (const char* e = rt_knob("RT_AMD_PRIMARY_CULL"))
+    if (atoi(e) == 0) return;
+  const HostArraysT<R>& A = H.arrays<R>();
+  const DevFlatSet& S = H.flat_sets[0];
+  for (int b = S.box_first; b < S.box_end && b - S.box_first < RT_CULL_BOXES && b < (int)A.boxes.size(); ++b) {
+    // the box {p : 0 <= a_k . p - sc_k <= 1}: corner s in {0, 1}^3 solves a_k . p = s_k + sc_k
+    const DevBoxT<R>& B = A.boxes[b];
+    const d3 rows[3] = {{(double)B.a0[0], (double)B.a0[1], (double)B.a0[2]},
+                        {(double)B.a1[0], (double)B.a1[1], (double)B.a1[2]},
+                        {(double)B.a2[0], (double)B.a2[1], (double)B.a2[2]}};
+    d3 c[8];
+    bool ok = true;
+    for (int i = 0; i < 8 && ok; ++i)
+      ok = solve3(rows, d3{(double)B.sc[0] + (i & 1), (double)B.sc[1] + (i >> 1 & 1), (double)B.sc[2] + (i >> 2 & 1)}, c[i]);
+    if (ok) cull_rect(P, c, 8, P.cull_box[b - S.box_first]);
+  }
+  for (int k = S.first; k < S.end_quad && k - S.first < RT_CULL_QUADS && 16 * (size_t)(k + 1) <= A.flat_recs.size(); ++k) {
+    // a static parallelogram record: n, q, wa, wb with wa . u = 1, wb . u = 0, n . u = 0 and
+    // wa . v = 0, wb . v = 1, n . v = 0 (rt_host_make_params' target has the same fields)
+    const R* f = A.flat_recs.data() + 16 * (size_t)k;
+    const d3 rows[3] = {{(double)f[8], (double)f[9], (double)f[10]},
+                        {(double)f[12], (double)f[13], (double)f[14]},
+                        {(double)f[0], (double)f[1], (double)f[2]}};
+    const d3 q = {(double)f[4], (double)f[5], (double)f[6]};
+    d3 u, v;
+    if (!solve3(rows, d3{1, 0, 0}, u) || !solve3(rows, d3{0, 1, 0}, v)) continue;
+    const d3 c[4] = {q, q + u, q + v, q + u + v};
+    cull_rect(P, c, 4, P.cull_quad[k - S.first]);
+  }
+}
+
 template <class R>
 SceneRecordsT<R> rt_host_records(const HostScene& H) {
   const HostArraysT<R>& A = H.arrays<R>();
@@ -1239,9 +1322,11 @@ int rt_host_render_params(const HostScene& H, int variant, const SceneRecordsT<R
   P.out_frame_rows = L.out_frame_rows;
   P.sample0 = L.sample0;
   rt_host_match_target(H, variant, P);
+  rt_host_cull_rects(H, P);
   return RT_OK;
 }
 #define RT_INSTANTIATE(R)                                                                                           \
+  template void rt_host_cull_rects<R>(const HostScene&, KernelParamsT<R>&);                                         \
   template int rt_host_match_target<R>(const HostScene&, int, KernelParamsT<R>&);                                   \
   template SceneRecordsT<R> rt_host_records<R>(const HostScene&);                                                   \
   template int rt_host_render_params<R>(const HostScene&, int, const SceneRecordsT<R>&, const rt_camera_settings*, \

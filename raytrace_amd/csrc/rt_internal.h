@@ -85,6 +85,19 @@
 #define RT_RING_AGG_PIX 8
 #define RT_RING_AGG_SLOTS_F64 6
 #define RT_RING_AGG_SLOTS_F32 5
+// The refill traces the camera segments itself (rt_trace.h lane_loop_flat_ring, RT_RING_PRIMARY): an
+// entry is then a path past its first segment and takes one more real and one more word (binary64:
+// 7216 B per wave).  Binary64 only: the FP32 ring has 192 B to spare below its legacy kernel's LDS,
+// not the 512 B the longer entries need, and keeps the loop that stores camera rays
+#ifndef RT_RING_PRIMARY_F64
+#define RT_RING_PRIMARY_F64 1
+#endif
+#define RT_RING_PRIMARY_F32 0
+// Screen rectangles for the camera segments' closest hit (KernelParams::cull_box / cull_quad): the
+// first RT_CULL_BOXES box groups and RT_CULL_QUADS static parallelograms of the flat surface set
+// have one; later records are always tested
+#define RT_CULL_BOXES 8
+#define RT_CULL_QUADS 8
 #ifndef RT_BIG_CHUNK_MAX
 #define RT_BIG_CHUNK_MAX 16  // samples per big work item at most, synchronous calls (rt_build.cpp rt_host_plan_work)
 #endif
@@ -376,6 +389,14 @@ struct KernelParamsT {
   // tile pixel x spp + sample (one item size: big_items 0, chunk 1, n_chunks = spp), and the launch
   // runs rt_render_kernel_ring (rt_render_kernel.h).  0: items are chunks, the legacy loops
   int flat_ring;
+  // Screen rectangles of the flat surface set's first box groups and static parallelograms
+  // (rt_build.cpp rt_host_cull_rects, in rt_host_render_params; read by rt_trace.h
+  // closest_flat_primary): {gy0 << 16 | px0, gy1 << 16 | px1} in the frame's global pixel
+  // coordinates (as pxgy).  No camera ray through a pixel outside [px0, px1] x [gy0, gy1] meets the
+  // record.  {0, 0xffffffff}: every pixel (a defocus camera, a corner not in front of the camera;
+  // env RT_AMD_PRIMARY_CULL=0, experiments, for every record)
+  uint32_t cull_box[RT_CULL_BOXES][2];
+  uint32_t cull_quad[RT_CULL_QUADS][2];
 };
 using DevMaterial = DevMaterialT<float>;
 using DevTexture = DevTextureT<float>;
@@ -498,6 +519,12 @@ int rt_host_render_params(const HostScene& H, int variant, const SceneRecordsT<R
 // the deferred redirect pdf alone (part of rt_host_render_params), from P's targets and H's records; returns target_defer
 template <class R>
 int rt_host_match_target(const HostScene& H, int variant, KernelParamsT<R>& P);
+// the camera segments' screen rectangles alone (part of rt_host_render_params): P.cull_box / P.cull_quad
+// from P's camera and H's flat surface set; "every pixel" for a defocus camera, a record with a
+// corner not strictly in front of the camera, a scene that is not flat, and under env
+// RT_AMD_PRIMARY_CULL=0 (experiments)
+template <class R>
+void rt_host_cull_rects(const HostScene& H, KernelParamsT<R>& P);
 // work decomposition (rt_build.cpp): chunk so that items >= ~8 x resident lanes
 template <class R>
 void rt_host_plan_work(KernelParamsT<R>& P, long long resident_lanes, bool two_sizes, bool lone = false);  // two_sizes: flat kernel

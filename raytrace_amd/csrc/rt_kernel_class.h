@@ -181,14 +181,20 @@ constexpr size_t rt_class_lds_bytes(bool f64, KernelClass c, int stack_depth, in
 // lane_loop_flat_ring): one class has it, in both precisions — flat, constant textures, the diffuse
 // materials, no media (the Cornell box) — as a kernel of its own beside the class's legacy one, at
 // the class's occupancy.  LDS of its one-wave workgroup: the ring's 64 rays (6 reals and 4 words
-// each), then the aggregation slots (rt_internal.h RT_RING_*); never more than the legacy kernel's.
+// each; 7 and 5 where the refill traces the camera segments, rt_ring_primary), then the aggregation
+// slots (rt_internal.h RT_RING_*); never more than the legacy kernel's.
 constexpr KernelClass rt_ring_class() { return KernelClass{RT_VAR_FLAT, 0, 0, false, false, 0, false}; }
 constexpr bool rt_class_has_ring(KernelClass c) {
   return c.var == RT_VAR_FLAT && c.tex == 0 && c.media == 0 && !c.mats && !c.inst;
 }
 constexpr int rt_ring_agg_slots(bool f64) { return f64 ? RT_RING_AGG_SLOTS_F64 : RT_RING_AGG_SLOTS_F32; }
 constexpr int rt_ring_agg_bytes(bool f64) { return rt_ring_agg_slots(f64) * (RT_RING_AGG_PIX * rt_acc_words(f64) * 8 + 2 * 4); }
-constexpr int rt_ring_ray_bytes(bool f64) { return RT_RING_LANES * (6 * (f64 ? 8 : 4) + 4 * 4); }
+// (an entry of the form that traces the camera segments at the refill, rt_internal.h
+// RT_RING_PRIMARY_*: one more real, the scatter's weight, and one more word, leaf left and primitive)
+constexpr bool rt_ring_primary(bool f64) { return f64 ? RT_RING_PRIMARY_F64 != 0 : RT_RING_PRIMARY_F32 != 0; }
+constexpr int rt_ring_reals(bool f64) { return rt_ring_primary(f64) ? 7 : 6; }
+constexpr int rt_ring_words(bool f64) { return rt_ring_primary(f64) ? 5 : 4; }
+constexpr int rt_ring_ray_bytes(bool f64) { return RT_RING_LANES * (rt_ring_reals(f64) * (f64 ? 8 : 4) + rt_ring_words(f64) * 4); }
 constexpr size_t rt_ring_lds_bytes(bool f64) { return (size_t)rt_ring_ray_bytes(f64) + rt_ring_agg_bytes(f64); }
 static_assert(RT_BLOCK == RT_RING_LANES, "the ring belongs to a one-wave workgroup");
 static_assert(rt_ring_lds_bytes(false) <= rt_class_fixed_lds(false, rt_ring_class()) &&

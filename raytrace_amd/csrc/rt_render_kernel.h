@@ -418,7 +418,13 @@ void rt_render_kernel(KernelParams P) {
   if (overflow) atomicOr(P.status, 1);
 }
 
-#if !RT_TU_NOLICM  // (the main translation unit: rt_ring_class is compiled with MachineLICM)
+// The ring kernel's translation unit.  The form that stores camera rays (FP32) is compiled with
+// MachineLICM, as rt_ring_class's legacy kernel.  The form that traces the camera segments at the
+// refill (RT_RING_PRIMARY_*; binary64) holds a second closest hit and shade while the other lanes'
+// paths are live: with the pass's hoisted constants on top it spilled 44 VGPRs at the class's 5
+// waves; without the pass it fits the 96 VGPRs with none
+#define RT_RING_NOLICM (RT_F64 ? RT_RING_PRIMARY_F64 : RT_RING_PRIMARY_F32)
+#if RT_TU_NOLICM == RT_RING_NOLICM
 // The ring form of rt_ring_class's kernel (rt_trace.h lane_loop_flat_ring; launched when
 // KernelParams::flat_ring): a one-wave workgroup at the class's occupancy floor.  LDS: the ring's
 // rays, then this wave's aggregation slots (rt_kernel_class.h rt_ring_lds_bytes).
@@ -426,8 +432,8 @@ __global__ __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(rt_cla
 void rt_render_kernel_ring(KernelParams P) {
   extern __shared__ int smem[];
   real* ring_od = reinterpret_cast<real*>(smem);
-  uint32_t* ring_meta = reinterpret_cast<uint32_t*>(ring_od + 6 * RT_RING_LANES);
-  unsigned long long* agg = reinterpret_cast<unsigned long long*>(ring_meta + 4 * RT_RING_LANES);
+  uint32_t* ring_meta = reinterpret_cast<uint32_t*>(ring_od + rt_ring_reals(RT_F64) * RT_RING_LANES);
+  unsigned long long* agg = reinterpret_cast<unsigned long long*>(ring_meta + rt_ring_words(RT_F64) * RT_RING_LANES);
   constexpr int kAggBytes = rt_ring_agg_bytes(RT_F64);
   for (int i = (int)__lane_id(); i < kAggBytes / 8; i += 64) agg[i] = 0ull;
   WaveWork<rt_ring_agg_slots(RT_F64), RT_RING_AGG_PIX, true> work(P, (int)blockIdx.x, (int)gridDim.x, agg);
@@ -519,6 +525,17 @@ static int diag_read_both(int which, unsigned long long* out, size_t n) {
   delete[] other;
   return rc;
 }
+// the ring kernel, from whichever unit holds it (RT_RING_NOLICM)
+#if RT_RING_NOLICM
+render_fn ring_kernel_nolicm();
+#if RT_TU_NOLICM
+render_fn ring_kernel_nolicm() { return rt_render_kernel_ring; }
+#else
+static render_fn ring_kernel_of() { return ring_kernel_nolicm(); }
+#endif
+#elif !RT_TU_NOLICM
+static render_fn ring_kernel_of() { return rt_render_kernel_ring; }
+#endif
 #if RT_TU_NOLICM
 render_fn render_kernel_nolicm(int variant) { return render_kernel_this_tu(variant); }
 #else
@@ -558,7 +575,7 @@ int rt_launch_render(const KernelParamsT<RT_NS::real>& p, int grid_blocks, int v
   int grid = need < grid_blocks ? (int)need : grid_blocks;
   if (p.flat_ring) {  // the ring form's plan (rt_build.cpp rt_host_plan_ring): its kernel, or none
     if (!rt_class_has_ring(c)) return -1;
-    hipLaunchKernelGGL(rt_render_kernel_ring, dim3(grid), dim3(block), rt_ring_lds_bytes(RT_F64), (hipStream_t)stream, p);
+    hipLaunchKernelGGL(ring_kernel_of(), dim3(grid), dim3(block), rt_ring_lds_bytes(RT_F64), (hipStream_t)stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
   size_t lds = rt_class_lds_bytes(RT_F64, c, p.stack_depth, p.lds_nodes);

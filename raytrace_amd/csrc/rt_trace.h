@@ -1454,6 +1454,45 @@ RT_FN void closest_flat(const KernelParams& P, int set, const RayCtx& R, real tm
 #endif
   }
 }
+// closest_flat of the surface set for camera rays, the wave's lanes together (the ring loop's refill,
+// lane_loop_flat_ring): a box group or static parallelogram whose screen rectangle (KernelParams::
+// cull_box / cull_quad, rt_build.cpp rt_host_cull_rects: outside it no camera ray meets the record)
+// holds no lane's pixel is not tested.  A skipped test would have reported a miss, which leaves C as
+// it is: the same closest hit.  The rectangles are scalar loads, the inside test integer compares,
+// the branch wave-uniform.  The redirect target's pdf term is left out: a path's first segment
+// left no scatter, and its own scatter sets the pdf anew.
+RT_FN bool cull_inside(const uint32_t (&r)[2], int px, int gy) {
+  return px >= (int)(r[0] & 0xffffu) && px <= (int)(r[1] & 0xffffu) && gy >= (int)(r[0] >> 16) && gy <= (int)(r[1] >> 16);
+}
+RT_FN void closest_flat_primary(const KernelParams& P, const RayCtx& R, uint32_t pxgy, Closest& C) {
+  const DevFlatSet& S = P.flat_sets[0];
+  const real tmin = kTmin, tmin_up = float_up(tmin);
+  const int gy = (int)(pxgy >> 16), px = (int)(pxgy & 0xffffu);
+  for (int b = S.box_first; b < S.box_end; ++b) {
+    const int j = b - S.box_first;
+    if (j < RT_CULL_BOXES && !RT_ANY(cull_inside(P.cull_box[j], px, gy))) continue;
+    test_box<true>((const RT_CAS DevBox*)P.boxes + b, R, tmin_up, C);
+  }
+  int k = S.first;
+  const RT_CAS PrimRec64* rp = (const RT_CAS PrimRec64*)P.flat_recs + k;
+  for (; k < S.end_quad; ++k, ++rp) {
+    const int j = k - S.first;
+    if (j < RT_CULL_QUADS && !RT_ANY(cull_inside(P.cull_quad[j], px, gy))) continue;
+    test_static<RT_PRIM_CLASS_QUAD>(ld_rec64(rp), R, tmin, tmin_up, C);
+  }
+  for (; k < S.end_tri; ++k, ++rp) test_static<RT_PRIM_CLASS_TRI>(ld_rec64(rp), R, tmin, tmin_up, C);
+  for (; k < S.end_sphere; ++k, ++rp) test_static<RT_PRIM_CLASS_SPHERE>(ld_rec64(rp), R, tmin, tmin_up, C);
+  for (; k < S.end; ++k, ++rp) test_rec<true>(P, ld_rec64(rp), k, R, tmin, tmin_up, C);
+#if RT_F64
+  if (C.t < kInf) C.prim = C.ord;  // (as closest_flat)
+#else
+  const uint32_t hi = (uint32_t)(C.key >> 32);
+  if (hi < 0x7f800000u) {
+    C.t = __builtin_bit_cast(real, hi);
+    C.prim = (int)(uint32_t)C.key;
+  }
+#endif
+}
 template <>
 RT_FN_SPEC void closest<true>(const KernelParams& P, cfp prims, int root, int set, const RayCtx& R, real tmin, Closest& C,
                          const Trav& W, int* overflow) {
@@ -1654,6 +1693,17 @@ RT_FN f3 normal_plus_unit_vector(f3 n, uint32_t a, uint32_t b, f3& uu) {
   return mk3(RFMA(r, c, n.x), RFMA(r, s, n.y), n.z + z);
 #endif
 }
+// What the deferring scatter leaves for the lane loop: the pdf's first term through a real*, or (the
+// ring loop's first segment, lane_loop_flat_ring) the scalar weight w of the throughput factor
+// Tf = w tex alone: the ring entry keeps w and the hit primitive, and the popping lane rebuilds
+// T = w tex and apdf = rem_prob w from them, the same products
+struct DeferW {
+  real w;
+};
+RT_FN void defer_put(real* a, real apdf, real) { *a = apdf; }
+RT_FN void defer_put(DeferW* a, real, real w) { a->w = w; }
+RT_FN void defer_put_w(real*, real) {}
+RT_FN void defer_put_w(DeferW* a, real w) { a->w = w; }
 template <bool kMats, bool kEarly, class... Defer>
 RT_FN bool mixture_scatter(const KernelParams& P, const HitInfo& h, const RayCtx& R, const u4& w, const DevMaterial& Mt,
                            bool hemi, f3 tex, f3& newdir, f3& Tf, Defer... apdf) {
@@ -1694,7 +1744,7 @@ RT_FN bool mixture_scatter(const KernelParams& P, const HitInfo& h, const RayCtx
     if (hemi && pdf1 <= RL(0.0)) return false;
   if constexpr (kDefer && !kMats && !kEarly) {
     if (P.target_defer) {  // wave-uniform (a kernel argument)
-      *(apdf, ...) = P.rem_prob * pdf1;
+      defer_put(apdf..., P.rem_prob * pdf1, pdf1);
       Tf = pdf1 * tex;
       newdir = dir;
       return !(hemi && pdf1 <= RL(0.0));
@@ -1719,7 +1769,9 @@ RT_FN bool mixture_scatter(const KernelParams& P, const HitInfo& h, const RayCtx
       f = ((RL(1.0) - g * g) * RT_RCP(base * RT_SQRT(base))) * f;
     }
   }
-  Tf = (pdf1 * RT_RCP(pdf)) * f;
+  const real wq = pdf1 * RT_RCP(pdf);
+  if constexpr (kDefer) defer_put_w(apdf..., wq);
+  Tf = wq * f;
   newdir = dir;
   return !(hemi && pdf1 <= RL(0.0));
 }
@@ -2226,6 +2278,18 @@ RT_FN int lane_loop_lockstep(const KernelParams& P0, Work& work, const Trav& TW,
 // the lanes commit what they still hold and the wave flushes once more.  No LDS beyond the ring.
 // Ring layout, word-major (entry i of array k at [k * 64 + i]: a wave's lanes touch consecutive
 // words): od = origin.xyz, direction.xyz; meta = time word, pixel, sample, tagged tile pixel.
+// RT_RING_PRIMARY (rt_internal.h; the binary64 kernel): the refill also TRACES the camera segments,
+// 64 lanes wide, with the closest hit culled per pixel (closest_flat_primary) — a third of all
+// segments, the most coherent ones, which otherwise run one by one beside secondary rays that need
+// every record tested.  A path that ends on its first segment is committed in the refill and takes
+// neither an entry nor a lane; one that goes on is stored as a path past its first segment: the hit
+// point and the new direction in od, a seventh real for the scatter's weight w, a fifth word for
+// (leaf left + 1) << 16 | hit primitive (a flat scene has at most RT_LDS_PRIMS_MAX leaves), and
+// the popping lane starts it at seg 1 with T = w x the primitive's colour and apdf = rem_prob w.
+#ifndef RT_RING_PRIMARY
+#define RT_RING_PRIMARY (RT_F64 ? RT_RING_PRIMARY_F64 : RT_RING_PRIMARY_F32)
+#endif
+static_assert(RT_LDS_PRIMS_MAX < 0xffff, "a ring entry packs the leaf left and the hit primitive in 16 bits each");
 RT_FN int wave_prefix(unsigned long long m) {  // set bits of m below this lane
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
@@ -2257,6 +2321,7 @@ RT_FN void flush_ring(Work& work, const real* ring_od, const uint32_t* ring_meta
 template <class Work>
 RT_FN void lane_loop_flat_ring(const KernelParams& P0, Work& work, real* ring_od, uint32_t* ring_meta) {
   constexpr int kN = RT_RING_LANES;
+  constexpr bool kPrimary = RT_RING_PRIMARY != 0;
   int cnt = 0;           // entries [0, cnt) of the ring hold rays not yet started (wave-uniform)
   int filled = 0;        // entries the last refill stored: popped ones hold finished samples (wave-uniform)
   bool drained = false;  // a refill met the end of the queues: nothing is left to claim (wave-uniform)
@@ -2293,9 +2358,21 @@ RT_FN void lane_loop_flat_ring(const KernelParams& P0, Work& work, real* ring_od
           tpk = (int)ring_meta[3 * kN + e];
           ring_od[e] = T.x, ring_od[kN + e] = T.y, ring_od[2 * kN + e] = T.z;
           ring_meta[3 * kN + e] = (uint32_t)held;
-          R.self_gid = -1;
-          T = mk3(RL(1.), RL(1.), RL(1.));
-          seg = 0;
+          if constexpr (kPrimary) {
+            // a path past its first segment (the refill traced it): the throughput and the deferred
+            // pdf from the scatter's weight and the hit primitive's colour, the products shade makes
+            const real w = ring_od[6 * kN + e];
+            const uint32_t gp = ring_meta[4 * kN + e];
+            const RT_CAS DevMaterial* Mp = (const RT_CAS DevMaterial*)P.prim_shade + (gp & 0xffffu);
+            R.self_gid = (int)(gp >> 16) - 1;
+            T = w * f3{Mp->c0[0], Mp->c0[1], Mp->c0[2]};
+            apdf = P.rem_prob * w;
+            seg = 1;
+          } else {
+            R.self_gid = -1;
+            T = mk3(RL(1.), RL(1.), RL(1.));
+            seg = 0;
+          }
           alive = true;
         }
         cnt -= take;
@@ -2314,6 +2391,41 @@ RT_FN void lane_loop_flat_ring(const KernelParams& P0, Work& work, real* ring_od
         const bool ok = in && open_item<true>(P, got, J);
         const int jt = work.tag_ring(J.tp, aslot);  // (with the pixel's place in the slot: WaveWork)
         work.skip_ring(in && !ok, jt);  // an id without a sample (a padding row, max_depth <= 0)
+        if constexpr (kPrimary) {
+          // the camera segments of the refill's samples, the lanes together: the closest hit culled
+          // per pixel (closest_flat_primary) and the shade of a path's first iteration (seg 0, no
+          // leaf left, throughput 1).  A path that ends here is committed here and gets no entry
+          bool go = false;
+          RayCtx C;
+          DeferW D{RL(0.)};
+          int gp = 0;
+          if (ok) {
+            camera_ray_flat(P, J.pix, J.sample, J.pxgy, C);
+            Closest H = no_hit();
+            closest_flat_primary(P, C, J.pxgy, H);
+            f3 L = mk3(RL(0.), RL(0.), RL(0.)), T1 = mk3(RL(1.), RL(1.), RL(1.));
+            int seg1 = 0;
+            go = !shade<0, false, false>(P, cf(P.prims), J.pix, J.sample, seg1, H.t, H.prim, -1, C, L, T1, -1, &D);
+            gp = (C.self_gid + 1) << 16 | H.prim;
+            if (!go) commit_sample_ring(work, jt, L);
+          }
+          const unsigned long long vm = __ballot(go);
+          if (go) {
+            const int e = wave_prefix(vm);
+            ring_od[e] = C.o.x, ring_od[kN + e] = C.o.y, ring_od[2 * kN + e] = C.o.z;
+            ring_od[3 * kN + e] = C.d.x, ring_od[4 * kN + e] = C.d.y, ring_od[5 * kN + e] = C.d.z;
+            ring_od[6 * kN + e] = D.w;
+            ring_meta[e] = C.time_w;
+            ring_meta[kN + e] = J.pix;
+            ring_meta[2 * kN + e] = (uint32_t)J.sample;
+            ring_meta[3 * kN + e] = (uint32_t)jt;
+            ring_meta[4 * kN + e] = (uint32_t)gp;
+          }
+          __builtin_amdgcn_wave_barrier();
+          filled = cnt = (int)__popcll(vm);
+          drained = __ballot(in) != ~0ull;
+          continue;
+        }
         const unsigned long long vm = __ballot(ok);
         if (ok) {
           RayCtx C;
