@@ -51,6 +51,8 @@ module Graphics.Ray.Device
   , Encoding(..), renderImage8, raytraceToFile
     -- * Ray queries on a resident scene (rt.h rt_scene_cast)
   , DeviceScene, withDeviceScene, hitMany, RtRay(..), RtHit(..)
+    -- * Radiance queries on a resident scene (rt.h rt_scene_radiance)
+  , radianceMany, cameraRays, RtPathRay(..), RtRadiance(..)
     -- * Geometry (Geometry.hs:5-16)
   , Geometry(Geometry), boundingBox, pureGeometry, transform, moving
   , sphere, planeShape, parallelogram, cuboid, triangle, triangleMesh, constantMedium
@@ -81,7 +83,7 @@ import Data.List (sortOn)
 import Data.Functor.Identity (Identity)
 import Data.Int (Int32, Int64)
 import qualified Data.Map.Strict as Map
-import Data.Word (Word64, Word8)
+import Data.Word (Word32, Word64, Word8)
 import qualified Data.Massiv.Array as A
 import qualified Data.Massiv.Array.Unsafe as AU
 import Foreign
@@ -568,6 +570,11 @@ foreign import ccall safe "rt_scene_cast_async"
   c_rt_scene_cast_async :: Ptr () -> Ptr RtExec -> Ptr RtRay -> Ptr RtHit -> Int64 -> Int32 -> Ptr () -> IO CInt
 foreign import ccall safe "rt_scene_cast_status"
   c_rt_scene_cast_status :: Ptr () -> Ptr Int32 -> IO CInt
+foreign import ccall safe "rt_scene_radiance"
+  c_rt_scene_radiance :: Ptr () -> Ptr RtExec -> Ptr RtCamera -> Word64 -> Ptr RtPathRay -> Ptr RtRadiance -> Ptr () -> Int64
+                      -> Int32 -> Int32 -> IO CInt
+foreign import ccall safe "rt_scene_camera_rays"
+  c_rt_scene_camera_rays :: Ptr () -> Ptr RtExec -> Ptr RtCamera -> Word64 -> Int32 -> Ptr RtPathRay -> IO CInt
 foreign import ccall safe "rt_film_create"
   c_rt_film_create :: Ptr () -> Ptr RtCamera -> Word64 -> Ptr RtExec -> Ptr (Ptr ()) -> IO CInt
 foreign import ccall safe "rt_film_destroy"
@@ -658,6 +665,16 @@ foreign import ccall safe "rt_multi_film_frame"
 -- LAYOUT rt_hit.leaf 80
 -- LAYOUT rt_hit.instance 84
 -- LAYOUT rt_hit.material 88
+-- LAYOUT rt_path_ray 64
+-- LAYOUT rt_path_ray.origin 0
+-- LAYOUT rt_path_ray.dir 24
+-- LAYOUT rt_path_ray.time 48
+-- LAYOUT rt_path_ray.stream 56
+-- LAYOUT rt_path_ray.sample0 60
+-- LAYOUT rt_radiance 32
+-- LAYOUT rt_radiance.rgb 0
+-- LAYOUT rt_radiance.status 24
+-- LAYOUT rt_radiance.samples 28
 -- LAYOUT rt_exec 32
 -- LAYOUT rt_exec.flags 16
 -- LAYOUT rt_exec.n_devices 20
@@ -1070,6 +1087,73 @@ hitMany (DeviceScene scene) queries =
       | otherwise = Just ( HitRecord { hr_t = hitT h, hr_point = hitPoint h, hr_normal = hitNormal h
                                      , hr_frontSide = hitFront h /= 0, hr_uv = hitUV h }
                          , fromIntegral (hitMaterial h) )
+
+-- ---------------------------------------------------------------- radiance queries (rt.h rt_scene_radiance)
+
+-- | rt_path_ray (64 bytes): origin, direction (any non-zero length), time, the Philox stream (where a
+-- render puts the pixel id) and the ray's first sample index.
+data RtPathRay = RtPathRay { prOrigin :: !Vec3, prDir :: !Vec3, prTime :: !Double, prStream :: !Word32, prSample0 :: !Word32 }
+
+-- | rt_radiance (32 bytes).  radStatus: 1 ok, -1 malformed ray, 2 NaN-flagged.
+data RtRadiance = RtRadiance { radColor :: !Color, radStatus :: !Int32, radSamples :: !Word32 }
+
+instance Storable RtPathRay where
+  sizeOf _ = 64
+  alignment _ = 8
+  peek p = RtPathRay <$> peekV3 p 0 <*> peekV3 p 24 <*> peekD p 48 <*> peekByteOff p 56 <*> peekByteOff p 60
+  poke p (RtPathRay (V3 ox oy oz) (V3 dx dy dz) time stream s0) =
+    pokeDoubles p 0 [ox, oy, oz] >> pokeDoubles p 24 [dx, dy, dz] >> pokeDoubles p 48 [time]
+      >> pokeByteOff p 56 stream >> pokeByteOff p 60 s0
+
+instance Storable RtRadiance where
+  sizeOf _ = 32
+  alignment _ = 8
+  peek p = RtRadiance <$> peekV3 p 0 <*> peekByteOff p 24 <*> peekByteOff p 28
+  poke p (RtRadiance (V3 r g b) st n) = pokeDoubles p 0 [r, g, b] >> pokeI32 p 24 st >> pokeByteOff p 28 n
+
+-- one shard, binary64
+withPlainExec :: (Ptr RtExec -> IO a) -> IO a
+withPlainExec k = allocaBytes 32 $ \ex -> do
+  fillBytes ex 0 32
+  pokeI32 ex 4 (1 :: Int32)    -- n_shards
+  pokeI32 ex 12 (4 :: Int32)   -- row_block; flags 0: binary64
+  k (castPtr ex)
+
+-- | The reference's private @rayColor@ (Ray.hs:174-224) for many rays at once, in binary64: for each
+-- @(time, ray)@ the mean of @samples@ evaluations of @rayColor cs_maxRecursionDepth time ray@ with
+-- the settings' background and redirect targets (nothing else of the settings is read), media
+-- included.  Ray i draws from Philox stream i under the generator's key; the direction need not be
+-- unit.  Nothing for a malformed ray; a NaN-flagged ray is a NaN colour.  'NotReifiable' backgrounds
+-- and failing calls (RT_E_STACK included) are an 'IOError'.
+radianceMany :: DeviceScene -> R.CameraSettings -> StdGen -> Int -> [(Double, Ray)] -> IO [Maybe Color]
+radianceMany _ _ _ _ [] = pure []
+radianceMany (DeviceScene scene) settings gen samples queries =
+  case reifyBackground (R.cs_background settings) of
+    Nothing -> ioError (userError "rt_scene_radiance: the background is not reifiable")
+    Just bg ->
+      let n = length queries
+          rays = [ RtPathRay o d time i 0 | (i, (time, Ray o d)) <- zip [0 ..] queries ]
+      in withCamera settings bg $ \cam -> withArray rays $ \prays -> allocaArray n $ \pout -> withPlainExec $ \ex -> do
+           rc <- c_rt_scene_radiance scene ex cam (philoxKey gen) prays pout nullPtr (fromIntegral n) (fromIntegral samples) 0
+           if rc /= 0
+             then c_rt_last_error >>= peekCString >>= \msg -> ioError (userError ("rt_scene_radiance: " ++ msg))
+             else map (\r -> if radStatus r < 0 then Nothing else Just (radColor r)) <$> peekArray n pout
+
+-- | The rays @raytrace@'s device render makes for sample @sample@ of every pixel, row-major (unit
+-- directions, stream = the pixel id): traced with 'radianceMany''s call under RT_RADIANCE_UNIT_DIR
+-- they return that render's samples; through 'hitMany' they give G-buffers aligned with them.
+cameraRays :: DeviceScene -> R.CameraSettings -> StdGen -> Int -> IO [RtPathRay]
+cameraRays (DeviceScene scene) settings gen sample =
+  case reifyBackground (R.cs_background settings) of
+    Nothing -> ioError (userError "rt_scene_camera_rays: the background is not reifiable")
+    Just bg -> withCamera settings bg $ \cam -> withPlainExec $ \ex -> do
+      h <- fromIntegral <$> c_rt_image_height cam
+      let n = max 0 h * max 0 (R.cs_imageWidth settings)
+      allocaArray (max 1 n) $ \prays -> do
+        rc <- c_rt_scene_camera_rays scene ex cam (philoxKey gen) (fromIntegral sample) prays
+        if rc /= 0
+          then c_rt_last_error >>= peekCString >>= \msg -> ioError (userError ("rt_scene_camera_rays: " ++ msg))
+          else peekArray n prays
 
 -- | Render progressively on one GPU through a film (rt.h rt_film_*): passes of @batch@ samples
 -- until the frame's noise figure (rt_film_noise, checked from the second pass on) is at most

@@ -33,6 +33,7 @@
 #ifndef RT_AMD_H
 #define RT_AMD_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -583,6 +584,82 @@ int rt_scene_cast_async(const rt_device_scene* s, const rt_exec* ex, const rt_ra
 int rt_scene_cast(const rt_device_scene* s, const rt_exec* ex, const rt_ray* host_rays, rt_hit* host_hits, int64_t n,
                   int32_t flags);
 int rt_scene_cast_status(const rt_device_scene* s, int32_t* overflowed);
+
+/* Batched radiance queries on a resident scene: the path tracer on the caller's rays.
+ *
+ * rayColor (Ray.hs:174-224) is private to `raytrace` in the reference; rt_scene_radiance evaluates it
+ * for n rays of the caller: an orthographic or panoramic camera, irradiance probes, a lightmap.
+ * Unlike rt_scene_cast it draws random numbers, includes the `constantMedium` events and shades.
+ *
+ * rt_path_ray: ray i receives samples sample0 + [0, n_samples); each is ONE evaluation of
+ *   rayColor max_recursion_depth time ray.  Sample k uses the Philox words (stream, sample0 + k,
+ *   segment, event) under the key of `seed`, exactly as sample sample0 + k of a render's pixel whose
+ *   global id is `stream` does after its camera ray (the camera's own draws sit under events of their
+ *   own), so the ray a render makes for (pixel, sample) — rt_scene_camera_rays writes those — returns
+ *   that render's sample, word for word.  The direction may have any non-zero length and is
+ *   normalised as an rt_ray's; with RT_RADIANCE_UNIT_DIR it is unit already and its bits are used as
+ *   they stand (with RT_EXEC_F32: rounded to float).  time as rt_ray.time (24 bits).
+ * cs: only max_recursion_depth, the background and the redirect targets are read; the camera
+ *   geometry, image_width and samples_per_pixel are not.  max_recursion_depth <= 0: every sample is 0.
+ * rt_radiance: rgb is the mean over ALL samples the workspace holds for the ray, resolved as a film
+ *   pixel holding that many samples is (rt_film_resolve).  status 1: ok; -1: a malformed ray (a
+ *   non-finite field, a zero direction, time outside [0, 1]): nothing was added for it and rgb is 0;
+ *   2: some sample was NaN or out of the sums' range: rgb is NaN, as a film's flagged pixel.
+ * The workspace belongs to the caller: rt_scene_radiance_workspace_bytes(n, ex->flags) bytes, 16-byte
+ *   aligned, on the scene's device.  Per ray it holds W + 1 64-bit words, W = 6 (3 with RT_EXEC_F32):
+ *   the W fixed-point sum words in the film state's order (the high words of R, G, B in units of
+ *   2^-32; binary64: then their low words, units of 2^-64), then one word whose low 32 bits are the
+ *   NaN flag and whose high 32 bits are the ray's sample count.  Behind the n rays' words lie 16 bytes
+ *   of the kernel's own (its work cursor).  Without RT_RADIANCE_ACCUMULATE the call zeroes the
+ *   workspace on the stream first; with it the call adds onto what the workspace holds (of the same
+ *   n and precision), and rgb is the mean over the accumulated count.  Sums are integers: the result
+ *   does not depend on the schedule, and k calls of one sample accumulate to one call of k.
+ * Rays are neither sorted nor compacted and a wave waits for its longest path: 64 consecutive
+ *   (ray, sample chunk) items per wave, so the caller's ray order is the kernel's coherence.
+ *
+ * rt_scene_radiance_async: d_rays / d_out / d_workspace are device buffers on the scene's device;
+ *   enqueues on hip_stream.  ex gives the precision and must name no device list; the first call of
+ *   a precision uploads that precision's records and is not asynchronous, after that nothing is
+ *   allocated.  n == 0 is a no-op.  A traversal-stack overflow sets a word of the scene that stays
+ *   set until rt_scene_radiance_status reads it (as rt_scene_cast_status).
+ * rt_scene_radiance: the same from and to host buffers, synchronous; host_workspace may be NULL (the
+ *   call allocates and frees its own: RT_RADIANCE_ACCUMULATE then adds onto zeros) or a host copy of
+ *   the rays' words (n x (W + 1) words, without the tail), read before the call with
+ *   RT_RADIANCE_ACCUMULATE and written after it.  RT_E_STACK (results written) on overflow.
+ * rt_scene_camera_rays_async: for every pixel of cs's frame (rt_image_height(cs) x image_width,
+ *   row-major, one shard) the ray the render makes for sample `sample` of that pixel: origin, unit
+ *   direction (FP32 values widened exactly), time = the time word's 24 bits, stream = the global
+ *   pixel id, sample0 = sample.  Traced with RT_RADIANCE_UNIT_DIR and the same seed and precision
+ *   they return the render's samples; through rt_scene_cast they give G-buffers aligned with them.
+ * rt_scene_camera_rays: the same into a host buffer, synchronous.
+ * Null arguments, n < 0, n_samples <= 0 or above 2^24, unknown flags, a device list in ex and
+ *   n x n_samples at or above 2^31 - 2^18 (the item ids of one launch) are RT_E_INVALID before any device call. */
+#define RT_RADIANCE_UNIT_DIR 1
+#define RT_RADIANCE_ACCUMULATE 2
+typedef struct rt_path_ray {      /* 64 bytes, four 16-byte vectors */
+  double origin[3];
+  double dir[3];
+  double time;                    /* [0, 1] */
+  uint32_t stream;                /* Philox counter word 0: where a render puts the global pixel id */
+  uint32_t sample0;               /* first sample index of this ray in this call */
+} rt_path_ray;
+typedef struct rt_radiance {      /* 32 bytes */
+  double rgb[3];
+  int32_t status;                 /* 1 ok, -1 malformed ray, 2 flagged */
+  uint32_t samples;               /* samples the workspace holds for this ray after the call */
+} rt_radiance;
+size_t rt_scene_radiance_workspace_bytes(int64_t n, int32_t exec_flags);
+int rt_scene_radiance_async(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, uint64_t seed,
+                            const rt_path_ray* d_rays, rt_radiance* d_out, void* d_workspace, int64_t n, int32_t n_samples,
+                            int32_t flags, void* hip_stream);
+int rt_scene_radiance(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, uint64_t seed,
+                      const rt_path_ray* host_rays, rt_radiance* host_out, void* host_workspace, int64_t n,
+                      int32_t n_samples, int32_t flags);
+int rt_scene_radiance_status(const rt_device_scene* s, int32_t* overflowed);
+int rt_scene_camera_rays_async(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, uint64_t seed,
+                               int32_t sample, rt_path_ray* d_rays, void* hip_stream);
+int rt_scene_camera_rays(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, uint64_t seed,
+                         int32_t sample, rt_path_ray* host_rays);
 
 #ifdef __cplusplus
 }

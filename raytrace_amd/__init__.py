@@ -19,6 +19,7 @@ from .material import (Material, Texture, anisotropic, checkerTexture, constantT
                        isotropic, lambertian, lightSource, lommelSeeliger, marbleTexture, metal, mirror, noiseTexture,
                        pitchBlack, solidTexture, transparent, uvTexture)
 from .query import HIT_DTYPE, RAY_DTYPE, cast, hits_dict, make_rays
+from .radiance import PATH_RAY_DTYPE, RADIANCE_DTYPE, make_path_rays  # (the one-shot form: raytrace_amd.radiance.radiance)
 from .ray import DeviceScene, MultiDeviceScene, encode8, raytrace, readImage, render_shard, writeImage, writeImageSqrt
 from .scene import FlatScene, flatten
 

@@ -27,7 +27,11 @@ EXPORTED = ["rt_abi_version", "rt_last_error", "rt_device_count", "rt_image_heig
             "rt_multi_film_load", "rt_multi_film_frame", "rt_multi_film_copies",
             "rt_denoise_default_params", "rt_denoise_features", "rt_denoise_albedo", "rt_denoise_features_read", "rt_denoise_albedo_read", "rt_denoise_film",
             "rt_denoise_film_read",
-            "rt_scene_cast_async", "rt_scene_cast", "rt_scene_cast_status"]
+            "rt_scene_cast_async", "rt_scene_cast", "rt_scene_cast_status",
+            "rt_scene_radiance_async", "rt_scene_radiance", "rt_scene_radiance_status",
+            "rt_scene_camera_rays_async", "rt_scene_camera_rays"]
+# ... and the ones that return a size_t, not a status
+SIZE_FUNCTIONS = ["rt_scene_radiance_workspace_bytes"]
 
 
 class RtRedirectTarget(ctypes.Structure):
@@ -68,6 +72,8 @@ RT_EXEC_ENCODE8_SQRT = 4  # rt_render output: uint8 codes of writeImageSqrt
 RT_EXEC_SOLO = 8  # rt_render_async: the render runs alone (planned for a short end, as rt_render's)
 RT_QUERY_UV = 1  # rt_scene_cast flags: compute uv
 RT_QUERY_ANY_HIT = 2  # ... an occlusion query: only `hit` and some accepted `t`
+RT_RADIANCE_UNIT_DIR = 1  # rt_scene_radiance flags: dir is unit length already, used bit for bit
+RT_RADIANCE_ACCUMULATE = 2  # ... add to the workspace's sums instead of zeroing them first
 ENCODINGS = {None: 0, "srgb": RT_EXEC_ENCODE8_SRGB, "sqrt": RT_EXEC_ENCODE8_SQRT}
 ABI_VERSION = 6
 PRECISIONS = {"f64": np.float64, "f32": np.float32}
@@ -180,7 +186,18 @@ def load():
     L.rt_scene_cast_async.argtypes = [P, ctypes.POINTER(RtExec), P, P, ctypes.c_int64, ctypes.c_int32, P]
     L.rt_scene_cast.argtypes = [P, ctypes.POINTER(RtExec), P, P, ctypes.c_int64, ctypes.c_int32]
     L.rt_scene_cast_status.argtypes = [P, ctypes.POINTER(ctypes.c_int32)]
-    for name in EXPORTED:
+    L.rt_scene_radiance_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32]
+    L.rt_scene_radiance_workspace_bytes.restype = ctypes.c_size_t
+    L.rt_scene_radiance_async.argtypes = [P, ctypes.POINTER(RtExec), ctypes.POINTER(RtCameraSettings), ctypes.c_uint64, P, P, P,
+                                          ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, P]
+    L.rt_scene_radiance.argtypes = [P, ctypes.POINTER(RtExec), ctypes.POINTER(RtCameraSettings), ctypes.c_uint64, P, P, P,
+                                    ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
+    L.rt_scene_radiance_status.argtypes = [P, ctypes.POINTER(ctypes.c_int32)]
+    L.rt_scene_camera_rays_async.argtypes = [P, ctypes.POINTER(RtExec), ctypes.POINTER(RtCameraSettings), ctypes.c_uint64,
+                                             ctypes.c_int32, P, P]
+    L.rt_scene_camera_rays.argtypes = [P, ctypes.POINTER(RtExec), ctypes.POINTER(RtCameraSettings), ctypes.c_uint64,
+                                       ctypes.c_int32, P]
+    for name in EXPORTED + SIZE_FUNCTIONS:
         getattr(L, name)
     if L.rt_abi_version() != ABI_VERSION:
         raise RtDeviceError("librt_amd.so ABI version mismatch")

@@ -114,7 +114,8 @@ struct rt_device_scene {
   int device = 0;
   float* nodes = nullptr;
   int* perlin_perm = nullptr;
-  int* status = nullptr;     // 4 words: [0] the renders' stack overflow, [1] / [2] the asynchronous / synchronous casts'
+  int* status = nullptr;     // 8 words: [0] the renders' stack overflow, [1] / [2] the asynchronous / synchronous casts',
+                             // [4] / [5] the asynchronous / synchronous radiance queries'
   mutable int* prim_mat = nullptr;  // HostScene::prim_mat, uploaded by the first cast (rt_scene_cast*)
   // a precision's records are uploaded (and its kernel's occupancy queried) on its first render:
   // a caller that renders one precision never pays for the other's copy in HBM or its upload
@@ -437,7 +438,7 @@ int upload_common(const std::shared_ptr<const HostScene>& Hp, int device, rt_dev
   auto* s = new rt_device_scene();
   s->device = device;
   s->host = Hp;
-  std::vector<int> status(4, 0);
+  std::vector<int> status(8, 0);
   int rc;
   if ((rc = upload(&s->nodes, H.nodes)) || (rc = upload(&s->perlin_perm, H.perlin_perm)) ||
       (rc = upload(&s->status, status))) {
@@ -1026,6 +1027,77 @@ int cast_check(const rt_device_scene* s, const rt_exec* ex, const rt_ray* rays, 
   if (n < 0) return fail(RT_E_INVALID, "negative ray count %lld", (long long)n);
   if (flags & ~(RT_QUERY_UV | RT_QUERY_ANY_HIT)) return fail(RT_E_INVALID, "unknown query flags 0x%x", flags);
   if (ex->n_devices != 0) return fail(RT_E_INVALID, "a cast runs on the scene's device (n_devices = 0)");
+  return check_flags(ex);
+}
+
+// ---- radiance queries (include/rt.h rt_scene_radiance; rt_radiance.h)
+
+// the bytes of n rays' workspace words; the kernel's cursor lies behind them (16 bytes)
+size_t radiance_words_bytes(int64_t n, bool f32) { return (size_t)n * ((f32 ? 3 : 6) + 1) * sizeof(unsigned long long); }
+
+rt_exec one_shard(const rt_device_scene* s) {
+  rt_exec ex{};
+  ex.device = s->device;
+  ex.n_shards = 1;
+  ex.row_block = 4;
+  return ex;
+}
+
+// n rays of precision R enqueued on st: the workspace zeroed (or only its cursor, accumulate), the
+// path kernel, the resolve; a stack overflow sets the scene's status word `word`
+template <class R>
+int radiance_enqueue(const rt_device_scene* s, const rt_camera_settings* cs, uint64_t seed, const rt_path_ray* d_rays,
+                     rt_radiance* d_out, void* d_work, int64_t n, int n_samples, int flags, int word, hipStream_t st) {
+  if (int rc = ensure_precision<R>(s)) return rc;
+  const rt_camera_settings c1 = rt_host_radiance_camera(cs);
+  const rt_exec ex = one_shard(s);
+  KernelParamsT<R> P;
+  if (int rc = lane_params(s, &c1, seed, &ex, P, word)) return rc;
+  // (experiments and tests: fewer stack rows than the scene's BVH needs, the defined overflow path;
+  // samples per item — the result does not depend on it)
+  if (const char* e = rt_knob("RT_AMD_RADIANCE_STACK")) P.stack_depth = std::max(1, std::min(P.stack_depth, atoi(e)));
+  int chunk = 0;
+  if (const char* e = rt_knob("RT_AMD_RADIANCE_CHUNK")) chunk = std::max(0, atoi(e));
+  const size_t words = radiance_words_bytes(n, sizeof(R) == 4);
+  P.counter = (int*)((char*)d_work + words);
+  HIP_TRY(hipSetDevice(s->device));
+  if (flags & RT_RADIANCE_ACCUMULATE)
+    HIP_TRY(hipMemsetAsync(P.counter, 0, 16, st));
+  else
+    HIP_TRY(hipMemsetAsync(d_work, 0, words + 16, st));
+  if (rt_launch_radiance(P, s->variant, d_rays, d_out, (unsigned long long*)d_work, (long long)n, n_samples, chunk, flags, st))
+    return fail(RT_E_HIP, "radiance launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return RT_OK;
+}
+
+// the checks of a radiance query that need no device (rt_build.cpp rt_host_radiance_check, then the flags)
+int radiance_check(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, const void* rays, const void* out,
+                   int64_t n, int n_samples, int flags) {
+  std::string err;
+  if (int rc = rt_host_radiance_check(s, ex, cs, rays, out, n, n_samples, flags, err)) return fail(rc, "%s", err.c_str());
+  return check_flags(ex);
+}
+
+// the render's camera rays of (cs, seed, sample) in precision R enqueued on st
+template <class R>
+int camera_rays_enqueue(const rt_device_scene* s, const rt_camera_settings* cs, uint64_t seed, int sample, rt_path_ray* d_rays,
+                        hipStream_t st) {
+  if (int rc = ensure_precision<R>(s)) return rc;
+  const rt_exec ex = one_shard(s);
+  KernelParamsT<R> P;
+  if (int rc = lane_params(s, cs, seed, &ex, P)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  if (rt_launch_camera_rays(P, s->variant, d_rays, sample, st))
+    return fail(RT_E_HIP, "camera-ray launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return RT_OK;
+}
+int camera_rays_check(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, int sample, const void* rays) {
+  if (!s) return fail(RT_E_INVALID, "null scene");
+  if (!ex) return fail(RT_E_INVALID, "null rt_exec");
+  if (!cs) return fail(RT_E_INVALID, "null camera settings");
+  if (!rays) return fail(RT_E_INVALID, "null ray buffer");
+  if (sample < 0) return fail(RT_E_INVALID, "negative sample index %d", sample);
+  if (ex->n_devices != 0) return fail(RT_E_INVALID, "camera rays are made on the scene's device (n_devices = 0)");
   return check_flags(ex);
 }
 
@@ -1945,6 +2017,87 @@ int rt_scene_cast_status(const rt_device_scene* s, int32_t* overflowed) {
   if (status) HIP_TRY(hipMemset(s->status + 1, 0, sizeof(int)));
   *overflowed = status ? 1 : 0;
   return RT_OK;
+}
+
+size_t rt_scene_radiance_workspace_bytes(int64_t n, int32_t exec_flags) {
+  return radiance_words_bytes(n < 0 ? 0 : n, (exec_flags & RT_EXEC_F32) != 0) + 16;
+}
+
+int rt_scene_radiance_async(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, uint64_t seed,
+                            const rt_path_ray* d_rays, rt_radiance* d_out, void* d_workspace, int64_t n, int32_t n_samples,
+                            int32_t flags, void* hip_stream) {
+  if (int rc = radiance_check(s, ex, cs, d_rays, d_out, n, n_samples, flags)) return rc;
+  if (!d_workspace) return fail(RT_E_INVALID, "null workspace");
+  if (n == 0) return RT_OK;
+  return exec_f32(ex)
+             ? radiance_enqueue<float>(s, cs, seed, d_rays, d_out, d_workspace, n, n_samples, flags, 4, (hipStream_t)hip_stream)
+             : radiance_enqueue<double>(s, cs, seed, d_rays, d_out, d_workspace, n, n_samples, flags, 4, (hipStream_t)hip_stream);
+}
+
+int rt_scene_radiance(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, uint64_t seed,
+                      const rt_path_ray* host_rays, rt_radiance* host_out, void* host_workspace, int64_t n,
+                      int32_t n_samples, int32_t flags) {
+  if (int rc = radiance_check(s, ex, cs, host_rays, host_out, n, n_samples, flags)) return rc;
+  if (n == 0) return RT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  char* mem = nullptr;
+  const size_t ray_bytes = (size_t)n * sizeof(rt_path_ray), out_bytes = (size_t)n * sizeof(rt_radiance);
+  const size_t words = radiance_words_bytes(n, exec_f32(ex));
+  HIP_TRY(hipMalloc((void**)&mem, ray_bytes + out_bytes + words + 16));  // (each a multiple of 8 bytes, the first two of 16)
+  rt_path_ray* d_rays = (rt_path_ray*)mem;
+  rt_radiance* d_out = (rt_radiance*)(mem + ray_bytes);
+  char* d_work = mem + ray_bytes + out_bytes;
+  const bool keep = host_workspace && (flags & RT_RADIANCE_ACCUMULATE);
+  int status = 0;
+  int rc = RT_OK;
+  if (hipMemcpy(d_rays, host_rays, ray_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      (keep ? hipMemcpy(d_work, host_workspace, words, hipMemcpyHostToDevice) : hipMemset(d_work, 0, words)) != hipSuccess ||
+      hipMemset(s->status + 5, 0, sizeof(int)) != hipSuccess)
+    rc = fail(RT_E_HIP, "ray upload failed: %s", hipGetErrorString(hipGetLastError()));
+  if (!rc)
+    rc = exec_f32(ex) ? radiance_enqueue<float>(s, cs, seed, d_rays, d_out, d_work, n, n_samples, flags, 5, nullptr)
+                      : radiance_enqueue<double>(s, cs, seed, d_rays, d_out, d_work, n, n_samples, flags, 5, nullptr);
+  if (!rc && (hipMemcpy(host_out, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+              (host_workspace && hipMemcpy(host_workspace, d_work, words, hipMemcpyDeviceToHost) != hipSuccess) ||
+              hipMemcpy(&status, s->status + 5, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess))
+    rc = fail(RT_E_HIP, "radiance read-back failed: %s", hipGetErrorString(hipGetLastError()));
+  (void)hipFree(mem);
+  if (!rc && status) return fail(RT_E_STACK, "BVH traversal stack overflow");
+  return rc;
+}
+
+int rt_scene_radiance_status(const rt_device_scene* s, int32_t* overflowed) {
+  if (!s || !overflowed) return fail(RT_E_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  int status = 0;
+  HIP_TRY(hipMemcpy(&status, s->status + 4, sizeof(int), hipMemcpyDeviceToHost));
+  if (status) HIP_TRY(hipMemset(s->status + 4, 0, sizeof(int)));
+  *overflowed = status ? 1 : 0;
+  return RT_OK;
+}
+
+int rt_scene_camera_rays_async(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, uint64_t seed,
+                               int32_t sample, rt_path_ray* d_rays, void* hip_stream) {
+  if (int rc = camera_rays_check(s, ex, cs, sample, d_rays)) return rc;
+  return exec_f32(ex) ? camera_rays_enqueue<float>(s, cs, seed, sample, d_rays, (hipStream_t)hip_stream)
+                      : camera_rays_enqueue<double>(s, cs, seed, sample, d_rays, (hipStream_t)hip_stream);
+}
+
+int rt_scene_camera_rays(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, uint64_t seed,
+                         int32_t sample, rt_path_ray* host_rays) {
+  if (int rc = camera_rays_check(s, ex, cs, sample, host_rays)) return rc;
+  const int h = rt_host_image_height(cs);
+  if (h <= 0 || cs->image_width <= 0) return fail(RT_E_INVALID, "bad image size");
+  const size_t bytes = (size_t)h * (size_t)cs->image_width * sizeof(rt_path_ray);
+  HIP_TRY(hipSetDevice(s->device));
+  rt_path_ray* d = nullptr;
+  HIP_TRY(hipMalloc((void**)&d, bytes));
+  int rc = exec_f32(ex) ? camera_rays_enqueue<float>(s, cs, seed, sample, d, nullptr)
+                        : camera_rays_enqueue<double>(s, cs, seed, sample, d, nullptr);
+  if (!rc && hipMemcpy(host_rays, d, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    rc = fail(RT_E_HIP, "camera-ray read-back failed: %s", hipGetErrorString(hipGetLastError()));
+  (void)hipFree(d);
+  return rc;
 }
 
 #if defined(RT_PHASE_PROF)

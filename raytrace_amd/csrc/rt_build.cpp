@@ -1515,3 +1515,42 @@ void rt_host_encode8_thresholds(int encoding, double* thr) {
   const double* t = encoding == 1 ? kEnc8Sqrt : kEnc8Srgb;
   for (int k = 0; k < 256; ++k) thr[k] = t[k];
 }
+
+// ---- radiance queries (include/rt.h rt_scene_radiance): what needs no device
+
+// the frame a radiance query's argument block is made for: a valid 1 x 1 camera (as a cast's) with
+// the caller's depth, background and redirect targets — nothing else of cs is read
+rt_camera_settings rt_host_radiance_camera(const rt_camera_settings* cs) {
+  rt_camera_settings c{};
+  c.look_at[2] = -1.0;
+  c.up[1] = 1.0;
+  c.vfov = 1.0;
+  c.aspect_ratio = 1.0;
+  c.image_width = c.samples_per_pixel = 1;
+  c.focus_dist = 1.0;
+  c.max_recursion_depth = cs->max_recursion_depth;
+  c.background_kind = cs->background_kind;
+  std::memcpy(c.background_c0, cs->background_c0, sizeof c.background_c0);
+  std::memcpy(c.background_c1, cs->background_c1, sizeof c.background_c1);
+  c.n_redirect_targets = cs->n_redirect_targets;
+  c.redirect_targets = cs->redirect_targets;
+  return c;
+}
+
+int rt_host_radiance_check(const void* scene, const rt_exec* ex, const rt_camera_settings* cs, const void* rays, const void* out,
+                           int64_t n, int n_samples, int flags, std::string& err) {
+  if (!scene) return fail(err, RT_E_INVALID, "null scene");
+  if (!ex) return fail(err, RT_E_INVALID, "null rt_exec");
+  if (!cs) return fail(err, RT_E_INVALID, "null camera settings");
+  if (!rays) return fail(err, RT_E_INVALID, "null ray buffer");
+  if (!out) return fail(err, RT_E_INVALID, "null result buffer");
+  if (n < 0) return fail(err, RT_E_INVALID, "negative ray count %lld", (long long)n);
+  if (n_samples <= 0 || n_samples > RT_RADIANCE_MAX_SAMPLES)
+    return fail(err, RT_E_INVALID, "n_samples %d outside 1..%d", n_samples, RT_RADIANCE_MAX_SAMPLES);
+  if (flags & ~(RT_RADIANCE_UNIT_DIR | RT_RADIANCE_ACCUMULATE)) return fail(err, RT_E_INVALID, "unknown radiance flags 0x%x", flags);
+  if (ex->n_devices != 0) return fail(err, RT_E_INVALID, "a radiance query runs on the scene's device (n_devices = 0)");
+  if (n > (int64_t)RT_RADIANCE_MAX_IDS / n_samples)
+    return fail(err, RT_E_INVALID, "%lld rays x %d samples exceed the %d item ids of one call", (long long)n, n_samples,
+                RT_RADIANCE_MAX_IDS);
+  return RT_OK;
+}

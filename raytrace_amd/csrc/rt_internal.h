@@ -569,6 +569,28 @@ int rt_launch_list(const KernelParams& p, int variant, const rt_adaptive_rec* li
                    int chunk, void* stream);
 int rt_launch_list(const KernelParams64& p, int variant, const rt_adaptive_rec* list, const int* n_list, int n_samples,
                    int chunk, void* stream);
+// rt_radiance.hip / rt_radiance64_nl.hip: n_samples samples of each of the n rays (include/rt.h
+// rt_scene_radiance; rt_radiance.h; device pointers) added to the rays' workspace words `work`, then
+// resolved into `out`.  p as a render's (rt_host_render_params, any valid camera) with lds_nodes = 0,
+// status set and p.counter the kernel's zeroed item cursor; chunk > 0: samples per item.  -1 beyond
+// RT_RADIANCE_MAX_IDS items of one sample (the cursor's claims stay below 2^31 with room for one
+// claim per wave of the grid behind the end)
+#define RT_RADIANCE_MAX_IDS (0x7fffffff - (1 << 18))
+#define RT_RADIANCE_MAX_SAMPLES (1 << 24)  // samples of one call at most (a film's bound, rt_film.h RT_FILM_MAX_SAMPLES)
+// rt_build.cpp: a radiance query's frame (a valid 1 x 1 camera with cs's depth, background and
+// redirect targets) and the checks of its arguments that need no device (scene: any non-null pointer)
+rt_camera_settings rt_host_radiance_camera(const rt_camera_settings* cs);
+int rt_host_radiance_check(const void* scene, const rt_exec* ex, const rt_camera_settings* cs, const void* rays, const void* out,
+                           int64_t n, int n_samples, int flags, std::string& err);
+struct rt_path_ray;
+struct rt_radiance;
+int rt_launch_radiance(const KernelParams& p, int variant, const rt_path_ray* rays, rt_radiance* out, unsigned long long* work,
+                       long long n, int n_samples, int chunk, int flags, void* stream);
+int rt_launch_radiance(const KernelParams64& p, int variant, const rt_path_ray* rays, rt_radiance* out,
+                       unsigned long long* work, long long n, int n_samples, int chunk, int flags, void* stream);
+// the render's camera ray of (pixel, sample) for every pixel of p's frame (one shard), row-major
+int rt_launch_camera_rays(const KernelParams& p, int variant, rt_path_ray* rays, int sample, void* stream);
+int rt_launch_camera_rays(const KernelParams64& p, int variant, rt_path_ray* rays, int sample, void* stream);
 #if defined(RT_PHASE_PROF)
 int rt_prof_read_kernel(const KernelParams*, unsigned long long* out, int n);
 int rt_prof_read_kernel(const KernelParams64*, unsigned long long* out, int n);

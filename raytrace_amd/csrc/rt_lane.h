@@ -1,11 +1,12 @@
 // rt_lane.h — what the one-lane kernels share, for ONE precision: included after rt_trace.h of the same
-// RT_F64 (no include guard, as rt_trace.h's per-precision part) by rt_list.h, rt_features.h and
-// rt_query.h themselves — a translation unit includes one of the three per precision.  Their kernels
-// give a lane one thing to run to completion (a pixel's samples, a pixel's first hits, a ray)
+// RT_F64 (no include guard, as rt_trace.h's per-precision part) by rt_list.h, rt_features.h,
+// rt_query.h and rt_radiance.h themselves — a translation unit includes one of the four per precision.  Their kernels
+// give a lane one thing to run to completion (a pixel's samples, a pixel's first hits, a ray, a ray's paths)
 // instead of interleaving a work queue's paths as the render's lane loops do.
 //
 //   lane_query      one closest-hit query over a set, run by one lane from start to end
 //   segment_events  one path segment's events: the surface query, then the media in the class's mode
+//   lane_ray_begin  a caller's ray record as the ray a lane traces (the query and radiance kernels)
 // both the render's functions in the render's order (rt_trace.h lane_loop_lockstep for the flat
 // classes, lane_loop_bvh for the others), so that a pixel's path, its first hit and a query's hit
 // are the render's bit for bit; and the three launchers' shape.
@@ -35,6 +36,28 @@ RT_FN void lane_query(const KernelParams& P0, cfp prims, const Trav& W, RayCtx& 
     while (!trav_done(S) && !(any && S.C.prim >= 0)) trav_round<kInst, kLeaf>(P, R, S, W, overflow RT_PROF_NULLARG);
     C = S.C;
   }
+}
+
+// A caller's ray (include/rt.h rt_ray, rt_path_ray) as the ray a lane traces: the origin and the
+// direction converted to the kernel's precision and the time as the render's Philox word,
+// floor(time 2^24) << 8 (u01 of it is the time the kernel sees; a time of 1 is 1 - 2^-24).  The
+// direction is dir / |dir| in binary64, scaled by its largest component first (no overflow or
+// underflow of the squares); unit: the caller says it is unit already, its bits are used as they
+// stand.  The fields are finite, the direction is not zero and the time lies in [0, 1] (the callers'
+// own checks).  R is ray_clear'ed otherwise: the ray leaves no leaf.
+RT_FN void lane_ray_begin(const double (&o)[3], const double (&d)[3], double time, bool unit, RayCtx& R) {
+  ray_clear(R);
+  R.o = mk3((real)o[0], (real)o[1], (real)o[2]);
+  if (unit) {
+    R.d = mk3((real)d[0], (real)d[1], (real)d[2]);
+  } else {
+    const double m = fmax(fmax(fabs(d[0]), fabs(d[1])), fabs(d[2]));
+    const double dx = d[0] / m, dy = d[1] / m, dz = d[2] / m;
+    const double il = 1.0 / sqrt(dx * dx + dy * dy + dz * dz);
+    R.d = mk3((real)(dx * il), (real)(dy * il), (real)(dz * il));
+  }
+  const double tw = floor(time * 16777216.0);
+  R.time_w = (uint32_t)(tw > 16777215.0 ? 16777215.0 : tw) << 8;
 }
 
 // the event that ends a segment: a surface hit (prim, inst; t), a medium event (medium >= 0; t) or neither

@@ -43,16 +43,8 @@ RT_FN void query_ray(const KernelParams& P0, const real* prims_, const int* prim
   }
   const cfp prims = cf(prims_);
   const bool any = (flags & RT_QUERY_ANY_HIT) != 0;
-  // dir / |dir| in binary64, scaled by its largest component first (no overflow or underflow of the squares)
-  const double m = fmax(fmax(fabs(q.dir[0]), fabs(q.dir[1])), fabs(q.dir[2]));
-  const double dx = q.dir[0] / m, dy = q.dir[1] / m, dz = q.dir[2] / m;
-  const double il = 1.0 / sqrt(dx * dx + dy * dy + dz * dz);
   RayCtx R;
-  ray_clear(R);
-  R.o = mk3((real)q.origin[0], (real)q.origin[1], (real)q.origin[2]);
-  R.d = mk3((real)(dx * il), (real)(dy * il), (real)(dz * il));
-  const double tw = floor(q.time * 16777216.0);
-  R.time_w = (uint32_t)(tw > 16777215.0 ? 16777215.0 : tw) << 8;
+  lane_ray_begin(q.origin, q.dir, q.time, false, R);  // (shared with a radiance query's rays, rt_radiance.h)
   const real tmin = (real)q.tmin, tmax = (real)q.tmax;
   Closest C = no_hit();
   C.t = tmax;

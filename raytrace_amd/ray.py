@@ -179,6 +179,62 @@ class DeviceScene:
         _lib.check(self._lib.rt_scene_cast_status(self.handle, ctypes.byref(w)))
         return bool(w.value)
 
+    def radiance(self, origins, directions, settings: CameraSettings, seed, samples: int = 1, time=0.0, stream=None,
+                 sample0=0, precision: str = "f64", unit_dir: bool = False):
+        """The path tracer on n rays of the caller (rt_scene_radiance; raytrace_amd.radiance): each ray
+        receives samples sample0 + [0, samples) of Philox stream `stream` (default: the ray's index) and
+        returns their mean.  Of `settings` only cs_maxRecursionDepth, the background and the redirect
+        targets are read.  Returns (rgb (n, 3) float64, info) with info = dict(status (1 ok, -1 malformed
+        ray, 2 NaN-flagged), samples, work: the (n, words) uint64 workspace words)."""
+        from . import radiance as rad
+        rays = rad.make_path_rays(origins, directions, time, stream, sample0)
+        out, work = rad.radiance_records(self, rays, settings, seed, samples, precision, unit_dir)
+        return out["rgb"].copy(), dict(status=out["status"].copy(), samples=out["samples"].copy(), work=work)
+
+    def radiance_async(self, rays_ptr: int, out_ptr: int, work_ptr: int, n: int, samples: int, settings: CameraSettings,
+                       seed, stream_ptr: int = 0, accumulate: bool = False, unit_dir: bool = False,
+                       precision: str = "f64"):
+        """Enqueue `samples` samples of each of the n rt_path_ray records at rays_ptr (radiance.PATH_RAY_DTYPE)
+        into the rt_radiance records at out_ptr (radiance.RADIANCE_DTYPE), over the caller's workspace at
+        work_ptr (radiance.workspace_bytes(n, precision) bytes, 16-byte aligned) — device buffers, e.g.
+        torch uint8 tensors' data_ptr().  accumulate: add onto the workspace instead of zeroing it."""
+        from . import radiance as rad
+        cs = _lib.camera_struct(settings)
+        ex = _lib.exec_struct(device=self.device, precision=precision)
+        _lib.check(self._lib.rt_scene_radiance_async(self.handle, ctypes.byref(ex), ctypes.byref(cs), _seed64(seed),
+                                                     ctypes.c_void_p(rays_ptr), ctypes.c_void_p(out_ptr),
+                                                     ctypes.c_void_p(work_ptr), int(n), int(samples),
+                                                     rad.radiance_flags(unit_dir, accumulate),
+                                                     ctypes.c_void_p(stream_ptr or None)))
+
+    def radiance_overflowed(self) -> bool:
+        """Whether a radiance_async since the last call overflowed a traversal stack
+        (rt_scene_radiance_status); call after synchronising the queries' stream."""
+        w = ctypes.c_int32(0)
+        _lib.check(self._lib.rt_scene_radiance_status(self.handle, ctypes.byref(w)))
+        return bool(w.value)
+
+    def camera_rays(self, settings: CameraSettings, seed, sample: int = 0, precision: str = "f64") -> np.ndarray:
+        """The rays the render of (settings, seed, precision) makes for sample `sample` of every pixel,
+        row-major: (height x width,) radiance.PATH_RAY_DTYPE with unit directions, stream = the pixel id and
+        sample0 = sample (rt_scene_camera_rays).  Their radiance (unit_dir=True) is that render's sample."""
+        from . import radiance as rad
+        cs = _lib.camera_struct(settings)
+        ex = _lib.exec_struct(device=self.device, precision=precision)
+        rays = np.zeros(image_height(settings) * int(settings.cs_imageWidth), rad.PATH_RAY_DTYPE)
+        _lib.check(self._lib.rt_scene_camera_rays(self.handle, ctypes.byref(ex), ctypes.byref(cs), _seed64(seed), int(sample),
+                                                  rays.ctypes.data_as(ctypes.c_void_p)))
+        return rays
+
+    def camera_rays_async(self, rays_ptr: int, settings: CameraSettings, seed, sample: int = 0, stream_ptr: int = 0,
+                          precision: str = "f64"):
+        """camera_rays into a device buffer of height x width rt_path_ray records (rt_scene_camera_rays_async)."""
+        cs = _lib.camera_struct(settings)
+        ex = _lib.exec_struct(device=self.device, precision=precision)
+        _lib.check(self._lib.rt_scene_camera_rays_async(self.handle, ctypes.byref(ex), ctypes.byref(cs), _seed64(seed),
+                                                        int(sample), ctypes.c_void_p(rays_ptr),
+                                                        ctypes.c_void_p(stream_ptr or None)))
+
     def close(self):
         if self.handle:
             self._lib.rt_scene_destroy(self.handle)
