@@ -53,6 +53,8 @@ module Graphics.Ray.Device
   , DeviceScene, withDeviceScene, hitMany, RtRay(..), RtHit(..)
     -- * Radiance queries on a resident scene (rt.h rt_scene_radiance)
   , radianceMany, cameraRays, RtPathRay(..), RtRadiance(..)
+    -- * Ray orders: trace a batch in a coherence order (rt.h rt_scene_ray_order)
+  , rayOrder, hitManyOrdered, radianceManyOrdered
     -- * Geometry (Geometry.hs:5-16)
   , Geometry(Geometry), boundingBox, pureGeometry, transform, moving
   , sphere, planeShape, parallelogram, cuboid, triangle, triangleMesh, constantMedium
@@ -573,6 +575,13 @@ foreign import ccall safe "rt_scene_cast_status"
 foreign import ccall safe "rt_scene_radiance"
   c_rt_scene_radiance :: Ptr () -> Ptr RtExec -> Ptr RtCamera -> Word64 -> Ptr RtPathRay -> Ptr RtRadiance -> Ptr () -> Int64
                       -> Int32 -> Int32 -> IO CInt
+foreign import ccall safe "rt_scene_ray_order"
+  c_rt_scene_ray_order :: Ptr () -> Ptr RtRay -> Int64 -> Int32 -> Ptr Word32 -> IO CInt
+foreign import ccall safe "rt_scene_cast_ordered"
+  c_rt_scene_cast_ordered :: Ptr () -> Ptr RtExec -> Ptr RtRay -> Ptr RtHit -> Int64 -> Int32 -> Ptr Word32 -> IO CInt
+foreign import ccall safe "rt_scene_radiance_ordered"
+  c_rt_scene_radiance_ordered :: Ptr () -> Ptr RtExec -> Ptr RtCamera -> Word64 -> Ptr RtPathRay -> Ptr RtRadiance -> Ptr ()
+                              -> Int64 -> Int32 -> Int32 -> Ptr Word32 -> IO CInt
 foreign import ccall safe "rt_scene_camera_rays"
   c_rt_scene_camera_rays :: Ptr () -> Ptr RtExec -> Ptr RtCamera -> Word64 -> Int32 -> Ptr RtPathRay -> IO CInt
 foreign import ccall safe "rt_film_create"
@@ -1154,6 +1163,66 @@ cameraRays (DeviceScene scene) settings gen sample =
         if rc /= 0
           then c_rt_last_error >>= peekCString >>= \msg -> ioError (userError ("rt_scene_camera_rays: " ++ msg))
           else peekArray n prays
+
+-- ---------------------------------------------------------------- ray orders (rt.h rt_scene_ray_order)
+
+-- | The coherence order of a batch of rays (rt_scene_ray_order, RT_ORDER_RAYS): a permutation of
+-- @[0 .. n - 1]@, position i the index of the ray to trace i-th — rays sorted by the cell of their
+-- origin in the batch's own box, then by the cell of their direction, ties in index order.  It
+-- depends on origins and directions alone and on no scene (the scene names the device): compute it
+-- once for a batch that is traced many times.
+rayOrder :: DeviceScene -> [Ray] -> IO [Word32]
+rayOrder _ [] = pure []
+rayOrder (DeviceScene scene) rays =
+  let n = length rays
+  in withArray [ RtRay o d 0 1 0 | Ray o d <- rays ] $ \prays -> allocaArray n $ \porder -> do
+       rc <- c_rt_scene_ray_order scene prays (fromIntegral n) 0 porder   -- RT_ORDER_RAYS
+       if rc /= 0
+         then c_rt_last_error >>= peekCString >>= \msg -> ioError (userError ("rt_scene_ray_order: " ++ msg))
+         else peekArray n porder
+
+-- | 'hitMany' with the rays traced in an order (rt_scene_cast_ordered): @Just order@ — a permutation
+-- such as 'rayOrder''s, anything else is an 'IOError' — or @Nothing@ for the batch's own coherence
+-- order, computed on the device.  The results are 'hitMany''s, in the caller's indexing.
+hitManyOrdered :: DeviceScene -> Maybe [Word32] -> [(Double, Ray, Interval)] -> IO [Maybe (HitRecord, Int)]
+hitManyOrdered _ _ [] = pure []
+hitManyOrdered (DeviceScene scene) order queries =
+  let n = length queries
+      rays = [ RtRay o d tmin tmax time | (time, Ray o d, (tmin, tmax)) <- queries ]
+  in withArray rays $ \prays -> allocaArray n $ \phits -> maybeWith withArray (checkedOrder n order) $ \porder ->
+     withPlainExec $ \ex -> do
+       rc <- c_rt_scene_cast_ordered scene ex prays phits (fromIntegral n) 1 porder   -- RT_QUERY_UV
+       if rc /= 0
+         then c_rt_last_error >>= peekCString >>= \msg -> ioError (userError ("rt_scene_cast_ordered: " ++ msg))
+         else map toRecord <$> peekArray n phits
+  where
+    toRecord h
+      | hitFlag h /= 1 = Nothing
+      | otherwise = Just ( HitRecord { hr_t = hitT h, hr_point = hitPoint h, hr_normal = hitNormal h
+                                     , hr_frontSide = hitFront h /= 0, hr_uv = hitUV h }
+                         , fromIntegral (hitMaterial h) )
+
+-- | 'radianceMany' with the rays taken in an order (rt_scene_radiance_ordered), as 'hitManyOrdered'.
+radianceManyOrdered :: DeviceScene -> Maybe [Word32] -> R.CameraSettings -> StdGen -> Int -> [(Double, Ray)] -> IO [Maybe Color]
+radianceManyOrdered _ _ _ _ _ [] = pure []
+radianceManyOrdered (DeviceScene scene) order settings gen samples queries =
+  case reifyBackground (R.cs_background settings) of
+    Nothing -> ioError (userError "rt_scene_radiance_ordered: the background is not reifiable")
+    Just bg ->
+      let n = length queries
+          rays = [ RtPathRay o d time i 0 | (i, (time, Ray o d)) <- zip [0 ..] queries ]
+      in withCamera settings bg $ \cam -> withArray rays $ \prays -> allocaArray n $ \pout ->
+         maybeWith withArray (checkedOrder n order) $ \porder -> withPlainExec $ \ex -> do
+           rc <- c_rt_scene_radiance_ordered scene ex cam (philoxKey gen) prays pout nullPtr (fromIntegral n)
+                                             (fromIntegral samples) 0 porder
+           if rc /= 0
+             then c_rt_last_error >>= peekCString >>= \msg -> ioError (userError ("rt_scene_radiance_ordered: " ++ msg))
+             else map (\r -> if radStatus r < 0 then Nothing else Just (radColor r)) <$> peekArray n pout
+
+-- an order of the wrong length is made one the library refuses (its first entry out of range): the
+-- array handed over always holds n entries
+checkedOrder :: Int -> Maybe [Word32] -> Maybe [Word32]
+checkedOrder n = fmap (\o -> if length o == n then o else replicate n maxBound)
 
 -- | Render progressively on one GPU through a film (rt.h rt_film_*): passes of @batch@ samples
 -- until the frame's noise figure (rt_film_noise, checked from the second pass on) is at most

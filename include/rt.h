@@ -544,8 +544,9 @@ int rt_denoise_film_read(rt_film* f, const rt_denoise_params* p, void* host_out_
  *   RT_QUERY_ANY_HIT asks only WHETHER the interval holds a hit: hit is exactly the closest-hit
  *   query's, t is the distance of some accepted hit inside the interval, every other field is
  *   unspecified; the BVH classes leave their traversal at the first accepted hit.
- * Rays are neither sorted nor compacted: one lane per ray, 64 consecutive rays per wave, so the
- *   caller's ray order is the kernel's coherence.
+ * One lane per ray, 64 consecutive rays per wave, in the caller's order: that order is the kernel's
+ *   coherence.  rt_scene_cast_ordered (below) traces the same rays in a coherence order instead;
+ *   nothing is compacted.
  *
  * rt_scene_cast_async: d_rays / d_hits are device buffers of n records on the scene's device;
  *   enqueues on hip_stream.  ex gives the precision (RT_EXEC_F32) and must name no device list; the
@@ -614,8 +615,9 @@ int rt_scene_cast_status(const rt_device_scene* s, int32_t* overflowed);
  *   workspace on the stream first; with it the call adds onto what the workspace holds (of the same
  *   n and precision), and rgb is the mean over the accumulated count.  Sums are integers: the result
  *   does not depend on the schedule, and k calls of one sample accumulate to one call of k.
- * Rays are neither sorted nor compacted and a wave waits for its longest path: 64 consecutive
- *   (ray, sample chunk) items per wave, so the caller's ray order is the kernel's coherence.
+ * A wave takes 64 consecutive (ray, sample chunk) items in the caller's ray order and waits for its
+ *   longest path: that order is the kernel's coherence.  rt_scene_radiance_ordered (below) takes the
+ *   rays in a coherence order instead; nothing is compacted and no single lane is refilled.
  *
  * rt_scene_radiance_async: d_rays / d_out / d_workspace are device buffers on the scene's device;
  *   enqueues on hip_stream.  ex gives the precision and must name no device list; the first call of
@@ -660,6 +662,53 @@ int rt_scene_camera_rays_async(const rt_device_scene* s, const rt_exec* ex, cons
                                int32_t sample, rt_path_ray* d_rays, void* hip_stream);
 int rt_scene_camera_rays(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, uint64_t seed,
                          int32_t sample, rt_path_ray* host_rays);
+
+/* Ray orders: sort a batch by a coherence key once, trace it in that order as often as needed.
+ *
+ * The queries above give lane i record i.  An ORDER is a permutation of [0, n) as uint32: in the
+ * ordered calls lane i takes record order[i] and writes result order[i], so every buffer keeps the
+ * caller's indexing and the results are those of the unordered call, bit for bit (a radiance query's
+ * workspace words too: RT_RADIANCE_ACCUMULATE mixes ordered and unordered calls freely).  Only the
+ * grouping of rays into waves changes.
+ *
+ * rt_scene_ray_order_async computes the order of a batch on the device: a 30-bit key per ray — the
+ *   origin's cell in a 64^3 grid over the box of the batch's own origins (Morton order), then the
+ *   direction's cell in a 64 x 64 octahedral map (Morton order); DESIGN section 4g has the formula —
+ *   and a stable radix sort of (key, index).  The key reads only origin and dir, which rt_ray
+ *   (RT_ORDER_RAYS) and rt_path_ray (RT_ORDER_PATH_RAYS) share; a record with a non-finite value there
+ *   or a zero direction sorts last.  Equal keys keep their index order, so the order is a pure
+ *   function of the records.  It depends on no scene: s only names the device.  d_rays, d_order (n
+ *   uint32) and d_workspace (rt_ray_order_workspace_bytes(n) bytes, 16-byte aligned) are device
+ *   buffers; everything is enqueued on hip_stream, nothing is allocated or read back.  An order stays
+ *   valid while origins and directions do: tmin / tmax / time / sample0 may change between uses.
+ * rt_scene_ray_order: the same from and to host buffers, synchronous.
+ * rt_scene_cast_ordered_async / rt_scene_radiance_ordered_async: rt_scene_cast_async /
+ *   rt_scene_radiance_async with d_order, n uint32 on the device.  The order is trusted, except that
+ *   an entry >= n is skipped (nothing is read or written for it); an index that is missing from the
+ *   order leaves its result as it was, a repeated one is computed twice (a radiance query then adds
+ *   its samples twice).
+ * rt_scene_cast_ordered / rt_scene_radiance_ordered: the synchronous forms.  host_order NULL: the
+ *   call computes the order on the device and uses it, without a host round trip; otherwise it must
+ *   be a permutation of [0, n) (RT_E_INVALID if not).
+ * Status words, RT_E_STACK and the argument checks are the unordered calls'; in addition null
+ *   pointers, n < 0, n >= 2^31 and an unknown kind are RT_E_INVALID before any device call; n == 0 is
+ *   a no-op. */
+#define RT_ORDER_RAYS 0        /* records are rt_ray */
+#define RT_ORDER_PATH_RAYS 1   /* records are rt_path_ray */
+size_t rt_ray_order_workspace_bytes(int64_t n);
+int rt_scene_ray_order_async(const rt_device_scene* s, const void* d_rays, int64_t n, int32_t kind, uint32_t* d_order,
+                             void* d_workspace, void* hip_stream);
+int rt_scene_ray_order(const rt_device_scene* s, const void* host_rays, int64_t n, int32_t kind, uint32_t* host_order);
+int rt_scene_cast_ordered_async(const rt_device_scene* s, const rt_exec* ex, const rt_ray* d_rays, rt_hit* d_hits, int64_t n,
+                                int32_t flags, const uint32_t* d_order, void* hip_stream);
+int rt_scene_cast_ordered(const rt_device_scene* s, const rt_exec* ex, const rt_ray* host_rays, rt_hit* host_hits, int64_t n,
+                          int32_t flags, const uint32_t* host_order);
+int rt_scene_radiance_ordered_async(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, uint64_t seed,
+                                    const rt_path_ray* d_rays, rt_radiance* d_out, void* d_workspace, int64_t n,
+                                    int32_t n_samples, int32_t flags, const uint32_t* d_order, void* hip_stream);
+int rt_scene_radiance_ordered(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, uint64_t seed,
+                              const rt_path_ray* host_rays, rt_radiance* host_out, void* host_workspace, int64_t n,
+                              int32_t n_samples, int32_t flags, const uint32_t* host_order);
 
 #ifdef __cplusplus
 }

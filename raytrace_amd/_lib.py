@@ -29,9 +29,11 @@ EXPORTED = ["rt_abi_version", "rt_last_error", "rt_device_count", "rt_image_heig
             "rt_denoise_film_read",
             "rt_scene_cast_async", "rt_scene_cast", "rt_scene_cast_status",
             "rt_scene_radiance_async", "rt_scene_radiance", "rt_scene_radiance_status",
-            "rt_scene_camera_rays_async", "rt_scene_camera_rays"]
+            "rt_scene_camera_rays_async", "rt_scene_camera_rays",
+            "rt_scene_ray_order_async", "rt_scene_ray_order", "rt_scene_cast_ordered_async", "rt_scene_cast_ordered",
+            "rt_scene_radiance_ordered_async", "rt_scene_radiance_ordered"]
 # ... and the ones that return a size_t, not a status
-SIZE_FUNCTIONS = ["rt_scene_radiance_workspace_bytes"]
+SIZE_FUNCTIONS = ["rt_scene_radiance_workspace_bytes", "rt_ray_order_workspace_bytes"]
 
 
 class RtRedirectTarget(ctypes.Structure):
@@ -74,6 +76,7 @@ RT_QUERY_UV = 1  # rt_scene_cast flags: compute uv
 RT_QUERY_ANY_HIT = 2  # ... an occlusion query: only `hit` and some accepted `t`
 RT_RADIANCE_UNIT_DIR = 1  # rt_scene_radiance flags: dir is unit length already, used bit for bit
 RT_RADIANCE_ACCUMULATE = 2  # ... add to the workspace's sums instead of zeroing them first
+RT_ORDER_RAYS, RT_ORDER_PATH_RAYS = 0, 1  # rt_scene_ray_order kind: rt_ray / rt_path_ray records
 ENCODINGS = {None: 0, "srgb": RT_EXEC_ENCODE8_SRGB, "sqrt": RT_EXEC_ENCODE8_SQRT}
 ABI_VERSION = 6
 PRECISIONS = {"f64": np.float64, "f32": np.float32}
@@ -197,6 +200,17 @@ def load():
                                              ctypes.c_int32, P, P]
     L.rt_scene_camera_rays.argtypes = [P, ctypes.POINTER(RtExec), ctypes.POINTER(RtCameraSettings), ctypes.c_uint64,
                                        ctypes.c_int32, P]
+    L.rt_ray_order_workspace_bytes.argtypes = [ctypes.c_int64]
+    L.rt_ray_order_workspace_bytes.restype = ctypes.c_size_t
+    L.rt_scene_ray_order_async.argtypes = [P, P, ctypes.c_int64, ctypes.c_int32, P, P, P]
+    L.rt_scene_ray_order.argtypes = [P, P, ctypes.c_int64, ctypes.c_int32, P]
+    L.rt_scene_cast_ordered_async.argtypes = L.rt_scene_cast_async.argtypes[:-1] + [P, P]
+    L.rt_scene_cast_ordered.argtypes = L.rt_scene_cast.argtypes + [P]
+    L.rt_scene_radiance_ordered_async.argtypes = L.rt_scene_radiance_async.argtypes[:-1] + [P, P]
+    L.rt_scene_radiance_ordered.argtypes = L.rt_scene_radiance.argtypes + [P]
+    # (hooks outside rt.h: the host twin of the order, the sort alone and its tile)
+    L.rt_host_ray_order.argtypes = [P, ctypes.c_int64, ctypes.c_int32, P, P]
+    L.rt_order_sort_keys_async.argtypes = [ctypes.c_int32, P, ctypes.c_int64, P, P, P]
     for name in EXPORTED + SIZE_FUNCTIONS:
         getattr(L, name)
     if L.rt_abi_version() != ABI_VERSION:

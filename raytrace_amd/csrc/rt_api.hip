@@ -985,7 +985,7 @@ int film_features(rt_film* f, unsigned long long* feat, int n_feat, hipStream_t 
 // n queries of precision R enqueued on st; a stack overflow sets the scene's status word `word`
 template <class R>
 int cast_enqueue(const rt_device_scene* s, const rt_ray* d_rays, rt_hit* d_hits, int64_t n, int flags, int word,
-                 hipStream_t st) {
+                 hipStream_t st, const uint32_t* d_order = nullptr) {
   if (int rc = ensure_precision<R>(s)) return rc;
   {
     std::lock_guard<std::mutex> lock(s->mu);
@@ -1013,7 +1013,9 @@ int cast_enqueue(const rt_device_scene* s, const rt_ray* d_rays, rt_hit* d_hits,
   // (experiments and tests: fewer stack rows than the scene's BVH needs, the defined overflow path)
   if (const char* e = rt_knob("RT_AMD_CAST_STACK")) P.stack_depth = std::max(1, std::min(P.stack_depth, atoi(e)));
   HIP_TRY(hipSetDevice(s->device));
-  if (rt_launch_query(P, s->variant, d_rays, d_hits, s->prim_mat, (long long)n, flags, st))
+  // (lane i on record d_order[i]: the ordered units' kernels, rt_query_kernel.h RT_QUERY_ORDERED)
+  if (d_order ? rt_launch_query_ordered(P, s->variant, d_rays, d_hits, s->prim_mat, (long long)n, flags, d_order, st)
+              : rt_launch_query(P, s->variant, d_rays, d_hits, s->prim_mat, (long long)n, flags, st))
     return fail(RT_E_HIP, "query launch failed: %s", hipGetErrorString(hipGetLastError()));
   return RT_OK;
 }
@@ -1047,7 +1049,8 @@ rt_exec one_shard(const rt_device_scene* s) {
 // path kernel, the resolve; a stack overflow sets the scene's status word `word`
 template <class R>
 int radiance_enqueue(const rt_device_scene* s, const rt_camera_settings* cs, uint64_t seed, const rt_path_ray* d_rays,
-                     rt_radiance* d_out, void* d_work, int64_t n, int n_samples, int flags, int word, hipStream_t st) {
+                     rt_radiance* d_out, void* d_work, int64_t n, int n_samples, int flags, int word, hipStream_t st,
+                     const uint32_t* d_order = nullptr) {
   if (int rc = ensure_precision<R>(s)) return rc;
   const rt_camera_settings c1 = rt_host_radiance_camera(cs);
   const rt_exec ex = one_shard(s);
@@ -1065,7 +1068,10 @@ int radiance_enqueue(const rt_device_scene* s, const rt_camera_settings* cs, uin
     HIP_TRY(hipMemsetAsync(P.counter, 0, 16, st));
   else
     HIP_TRY(hipMemsetAsync(d_work, 0, words + 16, st));
-  if (rt_launch_radiance(P, s->variant, d_rays, d_out, (unsigned long long*)d_work, (long long)n, n_samples, chunk, flags, st))
+  if (d_order ? rt_launch_radiance_ordered(P, s->variant, d_rays, d_out, (unsigned long long*)d_work, (long long)n, n_samples,
+                                           chunk, flags, d_order, st)
+              : rt_launch_radiance(P, s->variant, d_rays, d_out, (unsigned long long*)d_work, (long long)n, n_samples, chunk,
+                                   flags, st))
     return fail(RT_E_HIP, "radiance launch failed: %s", hipGetErrorString(hipGetLastError()));
   return RT_OK;
 }
@@ -1099,6 +1105,123 @@ int camera_rays_check(const rt_device_scene* s, const rt_exec* ex, const rt_came
   if (sample < 0) return fail(RT_E_INVALID, "negative sample index %d", sample);
   if (ex->n_devices != 0) return fail(RT_E_INVALID, "camera rays are made on the scene's device (n_devices = 0)");
   return check_flags(ex);
+}
+
+// ---- ray orders (include/rt.h rt_scene_ray_order; rt_order.hip)
+
+// the checks of an order call that need no device
+int order_check(const rt_device_scene* s, const void* rays, int64_t n, int kind, const void* order) {
+  if (!s) return fail(RT_E_INVALID, "null scene");
+  if (!rays) return fail(RT_E_INVALID, "null ray buffer");
+  if (!order) return fail(RT_E_INVALID, "null order buffer");
+  if (n < 0) return fail(RT_E_INVALID, "negative ray count %lld", (long long)n);
+  if (n >= ((int64_t)1 << 31)) return fail(RT_E_INVALID, "%lld rays: an order holds fewer than 2^31", (long long)n);
+  if (kind != RT_ORDER_RAYS && kind != RT_ORDER_PATH_RAYS) return fail(RT_E_INVALID, "unknown record kind %d", kind);
+  return RT_OK;
+}
+int order_count_check(int64_t n) {
+  if (n >= ((int64_t)1 << 31)) return fail(RT_E_INVALID, "%lld rays: an order holds fewer than 2^31", (long long)n);
+  return RT_OK;
+}
+int order_stride(int kind) { return kind == RT_ORDER_RAYS ? (int)sizeof(rt_ray) : (int)sizeof(rt_path_ray); }
+// a host order is a permutation of [0, n)
+int permutation_check(const uint32_t* order, int64_t n) {
+  std::vector<bool> seen((size_t)n, false);
+  for (int64_t i = 0; i < n; ++i) {
+    const uint32_t v = order[i];
+    if ((int64_t)v >= n || seen[v]) return fail(RT_E_INVALID, "the order is no permutation of [0, %lld): entry %lld is %u", (long long)n, (long long)i, v);
+    seen[v] = true;
+  }
+  return RT_OK;
+}
+// The order of a synchronous ordered call into d_order (device, n uint32): the caller's host order
+// copied, or (null) computed on the device from d_rays with the scratch d_ws
+int order_for_sync(const uint32_t* host_order, const void* d_rays, int64_t n, int kind, uint32_t* d_order, void* d_ws) {
+  if (host_order) {
+    HIP_TRY(hipMemcpy(d_order, host_order, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return RT_OK;
+  }
+  if (rt_launch_ray_order(d_rays, (long long)n, order_stride(kind), d_order, d_ws, nullptr))
+    return fail(RT_E_HIP, "order launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return RT_OK;
+}
+size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// rt_scene_cast / rt_scene_cast_ordered: ordered with host_order null computes the order on the device
+int cast_sync(const rt_device_scene* s, const rt_exec* ex, const rt_ray* host_rays, rt_hit* host_hits, int64_t n, int flags,
+              bool ordered, const uint32_t* host_order) {
+  if (int rc = cast_check(s, ex, host_rays, host_hits, n, flags)) return rc;
+  if (ordered)
+    if (int rc = order_count_check(n)) return rc;
+  if (n == 0) return RT_OK;
+  if (ordered && host_order)
+    if (int rc = permutation_check(host_order, n)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  char* mem = nullptr;
+  const size_t ray_bytes = (size_t)n * sizeof(rt_ray), hit_bytes = (size_t)n * sizeof(rt_hit);
+  const size_t order_at = up256(ray_bytes + hit_bytes), ws_at = order_at + up256((size_t)n * sizeof(uint32_t));
+  const size_t total = !ordered ? ray_bytes + hit_bytes : ws_at + (host_order ? 0 : rt_order_workspace_bytes((long long)n));
+  HIP_TRY(hipMalloc((void**)&mem, total));  // (rays and hits both multiples of 16 bytes)
+  rt_ray* d_rays = (rt_ray*)mem;
+  rt_hit* d_hits = (rt_hit*)(mem + ray_bytes);
+  uint32_t* d_order = ordered ? (uint32_t*)(mem + order_at) : nullptr;
+  int status = 0;
+  int rc = RT_OK;
+  if (hipMemcpy(d_rays, host_rays, ray_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(s->status + 2, 0, sizeof(int)) != hipSuccess)
+    rc = fail(RT_E_HIP, "ray upload failed: %s", hipGetErrorString(hipGetLastError()));
+  if (!rc && ordered) rc = order_for_sync(host_order, d_rays, n, RT_ORDER_RAYS, d_order, mem + ws_at);
+  if (!rc)
+    rc = exec_f32(ex) ? cast_enqueue<float>(s, d_rays, d_hits, n, flags, 2, nullptr, d_order)
+                      : cast_enqueue<double>(s, d_rays, d_hits, n, flags, 2, nullptr, d_order);
+  if (!rc && (hipMemcpy(host_hits, d_hits, hit_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+              hipMemcpy(&status, s->status + 2, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess))
+    rc = fail(RT_E_HIP, "hit read-back failed: %s", hipGetErrorString(hipGetLastError()));
+  (void)hipFree(mem);
+  if (!rc && status) return fail(RT_E_STACK, "BVH traversal stack overflow");
+  return rc;
+}
+
+// rt_scene_radiance / rt_scene_radiance_ordered, as cast_sync
+int radiance_sync(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, uint64_t seed,
+                  const rt_path_ray* host_rays, rt_radiance* host_out, void* host_workspace, int64_t n, int n_samples, int flags,
+                  bool ordered, const uint32_t* host_order) {
+  if (int rc = radiance_check(s, ex, cs, host_rays, host_out, n, n_samples, flags)) return rc;
+  if (ordered)
+    if (int rc = order_count_check(n)) return rc;
+  if (n == 0) return RT_OK;
+  if (ordered && host_order)
+    if (int rc = permutation_check(host_order, n)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  char* mem = nullptr;
+  const size_t ray_bytes = (size_t)n * sizeof(rt_path_ray), out_bytes = (size_t)n * sizeof(rt_radiance);
+  const size_t words = radiance_words_bytes(n, exec_f32(ex));
+  const size_t plain = ray_bytes + out_bytes + words + 16;  // (each a multiple of 8 bytes, the first two of 16)
+  const size_t order_at = up256(plain), ws_at = order_at + up256((size_t)n * sizeof(uint32_t));
+  const size_t total = !ordered ? plain : ws_at + (host_order ? 0 : rt_order_workspace_bytes((long long)n));
+  HIP_TRY(hipMalloc((void**)&mem, total));
+  rt_path_ray* d_rays = (rt_path_ray*)mem;
+  rt_radiance* d_out = (rt_radiance*)(mem + ray_bytes);
+  char* d_work = mem + ray_bytes + out_bytes;
+  uint32_t* d_order = ordered ? (uint32_t*)(mem + order_at) : nullptr;
+  const bool keep = host_workspace && (flags & RT_RADIANCE_ACCUMULATE);
+  int status = 0;
+  int rc = RT_OK;
+  if (hipMemcpy(d_rays, host_rays, ray_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      (keep ? hipMemcpy(d_work, host_workspace, words, hipMemcpyHostToDevice) : hipMemset(d_work, 0, words)) != hipSuccess ||
+      hipMemset(s->status + 5, 0, sizeof(int)) != hipSuccess)
+    rc = fail(RT_E_HIP, "ray upload failed: %s", hipGetErrorString(hipGetLastError()));
+  if (!rc && ordered) rc = order_for_sync(host_order, d_rays, n, RT_ORDER_PATH_RAYS, d_order, mem + ws_at);
+  if (!rc)
+    rc = exec_f32(ex) ? radiance_enqueue<float>(s, cs, seed, d_rays, d_out, d_work, n, n_samples, flags, 5, nullptr, d_order)
+                      : radiance_enqueue<double>(s, cs, seed, d_rays, d_out, d_work, n, n_samples, flags, 5, nullptr, d_order);
+  if (!rc && (hipMemcpy(host_out, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+              (host_workspace && hipMemcpy(host_workspace, d_work, words, hipMemcpyDeviceToHost) != hipSuccess) ||
+              hipMemcpy(&status, s->status + 5, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess))
+    rc = fail(RT_E_HIP, "radiance read-back failed: %s", hipGetErrorString(hipGetLastError()));
+  (void)hipFree(mem);
+  if (!rc && status) return fail(RT_E_STACK, "BVH traversal stack overflow");
+  return rc;
 }
 
 // the checks of rt_denoise_film / _read that need no device; p: the parameters in effect
@@ -1985,28 +2108,7 @@ int rt_scene_cast_async(const rt_device_scene* s, const rt_exec* ex, const rt_ra
 
 int rt_scene_cast(const rt_device_scene* s, const rt_exec* ex, const rt_ray* host_rays, rt_hit* host_hits, int64_t n,
                   int32_t flags) {
-  if (int rc = cast_check(s, ex, host_rays, host_hits, n, flags)) return rc;
-  if (n == 0) return RT_OK;
-  HIP_TRY(hipSetDevice(s->device));
-  char* mem = nullptr;
-  const size_t ray_bytes = (size_t)n * sizeof(rt_ray), hit_bytes = (size_t)n * sizeof(rt_hit);
-  HIP_TRY(hipMalloc((void**)&mem, ray_bytes + hit_bytes));  // (both multiples of 16 bytes)
-  rt_ray* d_rays = (rt_ray*)mem;
-  rt_hit* d_hits = (rt_hit*)(mem + ray_bytes);
-  int status = 0;
-  int rc = RT_OK;
-  if (hipMemcpy(d_rays, host_rays, ray_bytes, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemset(s->status + 2, 0, sizeof(int)) != hipSuccess)
-    rc = fail(RT_E_HIP, "ray upload failed: %s", hipGetErrorString(hipGetLastError()));
-  if (!rc)
-    rc = exec_f32(ex) ? cast_enqueue<float>(s, d_rays, d_hits, n, flags, 2, nullptr)
-                      : cast_enqueue<double>(s, d_rays, d_hits, n, flags, 2, nullptr);
-  if (!rc && (hipMemcpy(host_hits, d_hits, hit_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
-              hipMemcpy(&status, s->status + 2, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess))
-    rc = fail(RT_E_HIP, "hit read-back failed: %s", hipGetErrorString(hipGetLastError()));
-  (void)hipFree(mem);
-  if (!rc && status) return fail(RT_E_STACK, "BVH traversal stack overflow");
-  return rc;
+  return cast_sync(s, ex, host_rays, host_hits, n, flags, false, nullptr);
 }
 
 int rt_scene_cast_status(const rt_device_scene* s, int32_t* overflowed) {
@@ -2037,33 +2139,7 @@ int rt_scene_radiance_async(const rt_device_scene* s, const rt_exec* ex, const r
 int rt_scene_radiance(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, uint64_t seed,
                       const rt_path_ray* host_rays, rt_radiance* host_out, void* host_workspace, int64_t n,
                       int32_t n_samples, int32_t flags) {
-  if (int rc = radiance_check(s, ex, cs, host_rays, host_out, n, n_samples, flags)) return rc;
-  if (n == 0) return RT_OK;
-  HIP_TRY(hipSetDevice(s->device));
-  char* mem = nullptr;
-  const size_t ray_bytes = (size_t)n * sizeof(rt_path_ray), out_bytes = (size_t)n * sizeof(rt_radiance);
-  const size_t words = radiance_words_bytes(n, exec_f32(ex));
-  HIP_TRY(hipMalloc((void**)&mem, ray_bytes + out_bytes + words + 16));  // (each a multiple of 8 bytes, the first two of 16)
-  rt_path_ray* d_rays = (rt_path_ray*)mem;
-  rt_radiance* d_out = (rt_radiance*)(mem + ray_bytes);
-  char* d_work = mem + ray_bytes + out_bytes;
-  const bool keep = host_workspace && (flags & RT_RADIANCE_ACCUMULATE);
-  int status = 0;
-  int rc = RT_OK;
-  if (hipMemcpy(d_rays, host_rays, ray_bytes, hipMemcpyHostToDevice) != hipSuccess ||
-      (keep ? hipMemcpy(d_work, host_workspace, words, hipMemcpyHostToDevice) : hipMemset(d_work, 0, words)) != hipSuccess ||
-      hipMemset(s->status + 5, 0, sizeof(int)) != hipSuccess)
-    rc = fail(RT_E_HIP, "ray upload failed: %s", hipGetErrorString(hipGetLastError()));
-  if (!rc)
-    rc = exec_f32(ex) ? radiance_enqueue<float>(s, cs, seed, d_rays, d_out, d_work, n, n_samples, flags, 5, nullptr)
-                      : radiance_enqueue<double>(s, cs, seed, d_rays, d_out, d_work, n, n_samples, flags, 5, nullptr);
-  if (!rc && (hipMemcpy(host_out, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
-              (host_workspace && hipMemcpy(host_workspace, d_work, words, hipMemcpyDeviceToHost) != hipSuccess) ||
-              hipMemcpy(&status, s->status + 5, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess))
-    rc = fail(RT_E_HIP, "radiance read-back failed: %s", hipGetErrorString(hipGetLastError()));
-  (void)hipFree(mem);
-  if (!rc && status) return fail(RT_E_STACK, "BVH traversal stack overflow");
-  return rc;
+  return radiance_sync(s, ex, cs, seed, host_rays, host_out, host_workspace, n, n_samples, flags, false, nullptr);
 }
 
 int rt_scene_radiance_status(const rt_device_scene* s, int32_t* overflowed) {
@@ -2099,6 +2175,85 @@ int rt_scene_camera_rays(const rt_device_scene* s, const rt_exec* ex, const rt_c
   (void)hipFree(d);
   return rc;
 }
+
+size_t rt_ray_order_workspace_bytes(int64_t n) { return rt_order_workspace_bytes((long long)n); }
+
+int rt_scene_ray_order_async(const rt_device_scene* s, const void* d_rays, int64_t n, int32_t kind, uint32_t* d_order,
+                             void* d_workspace, void* hip_stream) {
+  if (int rc = order_check(s, d_rays, n, kind, d_order)) return rc;
+  if (!d_workspace) return fail(RT_E_INVALID, "null workspace");
+  if (n == 0) return RT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  if (rt_launch_ray_order(d_rays, (long long)n, order_stride(kind), d_order, d_workspace, hip_stream))
+    return fail(RT_E_HIP, "order launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return RT_OK;
+}
+
+int rt_scene_ray_order(const rt_device_scene* s, const void* host_rays, int64_t n, int32_t kind, uint32_t* host_order) {
+  if (int rc = order_check(s, host_rays, n, kind, host_order)) return rc;
+  if (n == 0) return RT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t ray_bytes = up256((size_t)n * order_stride(kind)), order_bytes = up256((size_t)n * sizeof(uint32_t));
+  char* mem = nullptr;
+  HIP_TRY(hipMalloc((void**)&mem, ray_bytes + order_bytes + rt_order_workspace_bytes((long long)n)));
+  uint32_t* d_order = (uint32_t*)(mem + ray_bytes);
+  int rc = RT_OK;
+  if (hipMemcpy(mem, host_rays, (size_t)n * order_stride(kind), hipMemcpyHostToDevice) != hipSuccess)
+    rc = fail(RT_E_HIP, "ray upload failed: %s", hipGetErrorString(hipGetLastError()));
+  if (!rc) rc = order_for_sync(nullptr, mem, n, kind, d_order, mem + ray_bytes + order_bytes);
+  if (!rc && hipMemcpy(host_order, d_order, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+    rc = fail(RT_E_HIP, "order read-back failed: %s", hipGetErrorString(hipGetLastError()));
+  (void)hipFree(mem);
+  return rc;
+}
+
+int rt_scene_cast_ordered_async(const rt_device_scene* s, const rt_exec* ex, const rt_ray* d_rays, rt_hit* d_hits, int64_t n,
+                                int32_t flags, const uint32_t* d_order, void* hip_stream) {
+  if (int rc = cast_check(s, ex, d_rays, d_hits, n, flags)) return rc;
+  if (!d_order) return fail(RT_E_INVALID, "null order buffer");
+  if (int rc = order_count_check(n)) return rc;
+  if (n == 0) return RT_OK;
+  return exec_f32(ex) ? cast_enqueue<float>(s, d_rays, d_hits, n, flags, 1, (hipStream_t)hip_stream, d_order)
+                      : cast_enqueue<double>(s, d_rays, d_hits, n, flags, 1, (hipStream_t)hip_stream, d_order);
+}
+
+int rt_scene_cast_ordered(const rt_device_scene* s, const rt_exec* ex, const rt_ray* host_rays, rt_hit* host_hits, int64_t n,
+                          int32_t flags, const uint32_t* host_order) {
+  return cast_sync(s, ex, host_rays, host_hits, n, flags, true, host_order);
+}
+
+int rt_scene_radiance_ordered_async(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, uint64_t seed,
+                                    const rt_path_ray* d_rays, rt_radiance* d_out, void* d_workspace, int64_t n,
+                                    int32_t n_samples, int32_t flags, const uint32_t* d_order, void* hip_stream) {
+  if (int rc = radiance_check(s, ex, cs, d_rays, d_out, n, n_samples, flags)) return rc;
+  if (!d_workspace) return fail(RT_E_INVALID, "null workspace");
+  if (!d_order) return fail(RT_E_INVALID, "null order buffer");
+  if (int rc = order_count_check(n)) return rc;
+  if (n == 0) return RT_OK;
+  return exec_f32(ex) ? radiance_enqueue<float>(s, cs, seed, d_rays, d_out, d_workspace, n, n_samples, flags, 4,
+                                                (hipStream_t)hip_stream, d_order)
+                      : radiance_enqueue<double>(s, cs, seed, d_rays, d_out, d_workspace, n, n_samples, flags, 4,
+                                                 (hipStream_t)hip_stream, d_order);
+}
+
+int rt_scene_radiance_ordered(const rt_device_scene* s, const rt_exec* ex, const rt_camera_settings* cs, uint64_t seed,
+                              const rt_path_ray* host_rays, rt_radiance* host_out, void* host_workspace, int64_t n,
+                              int32_t n_samples, int32_t flags, const uint32_t* host_order) {
+  return radiance_sync(s, ex, cs, seed, host_rays, host_out, host_workspace, n, n_samples, flags, true, host_order);
+}
+
+// Test hooks outside rt.h: the sort alone over given keys (only read), and its tile
+int rt_order_sort_keys_async(int32_t device, const uint32_t* d_keys, int64_t n, uint32_t* d_order, void* d_workspace,
+                             void* hip_stream) {
+  if (n < 0 || n >= ((int64_t)1 << 31)) return fail(RT_E_INVALID, "bad key count %lld", (long long)n);
+  if (n == 0) return RT_OK;
+  if (!d_keys || !d_order || !d_workspace) return fail(RT_E_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(device));
+  if (rt_launch_order_sort(d_keys, (long long)n, d_order, d_workspace, hip_stream))
+    return fail(RT_E_HIP, "sort launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return RT_OK;
+}
+int rt_ray_order_tile(void) { return rt_order_tile(); }
 
 #if defined(RT_PHASE_PROF)
 // diagnostic build only: the BVH kernel's phase counters (rt_trace.h RT_PHASE_PROF), read and zeroed

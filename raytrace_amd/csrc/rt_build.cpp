@@ -31,6 +31,7 @@
 #include "rt_encode8_table.h"
 #include "rt_internal.h"
 #include "rt_kernel_class.h"
+#include "rt_order.h"
 
 const char* rt_knob(const char* name) {
   const char* on = std::getenv("RT_AMD_EXPERIMENTS");
@@ -1552,5 +1553,15 @@ int rt_host_radiance_check(const void* scene, const rt_exec* ex, const rt_camera
   if (n > (int64_t)RT_RADIANCE_MAX_IDS / n_samples)
     return fail(err, RT_E_INVALID, "%lld rays x %d samples exceed the %d item ids of one call", (long long)n, n_samples,
                 RT_RADIANCE_MAX_IDS);
+  return RT_OK;
+}
+
+// ---- ray orders (include/rt.h rt_scene_ray_order): the host twin of rt_order.hip from the same
+// header — the keys (keys_out, may be null) and their stable order (order_out, may be null) of n
+// records of `kind`.  A test hook, exported but not declared in rt.h.
+extern "C" int rt_host_ray_order(const void* rays, int64_t n, int32_t kind, uint32_t* keys_out, uint32_t* order_out) {
+  if (n < 0 || n >= ((int64_t)1 << 31) || (!rays && n > 0)) return RT_E_INVALID;
+  if (kind != RT_ORDER_RAYS && kind != RT_ORDER_PATH_RAYS) return RT_E_INVALID;
+  rt_order_host(rays, n, kind == RT_ORDER_RAYS ? sizeof(rt_ray) : sizeof(rt_path_ray), keys_out, order_out);
   return RT_OK;
 }

@@ -551,6 +551,13 @@ int rt_launch_resolve(const KernelParams64& p, void* stream);
 // (rt_host_render_params) with lds_nodes = 0 and status set
 int rt_launch_features(const KernelParams& p, int variant, unsigned long long* feat, int n_feat, void* stream);
 int rt_launch_features(const KernelParams64& p, int variant, unsigned long long* feat, int n_feat, void* stream);
+// rt_order.hip: the order of n ray records (include/rt.h rt_scene_ray_order; rt_order.h), device
+// pointers: keys of the records at `stride` bytes, a stable radix sort of (key, index), the indices
+// into d_order; rt_launch_order_sort: the sort alone over given keys (only read).  d_ws: rt_order_workspace_bytes(n)
+size_t rt_order_workspace_bytes(long long n);
+int rt_order_tile();  // pairs per workgroup per pass
+int rt_launch_ray_order(const void* d_rays, long long n, int stride, uint32_t* d_order, void* d_ws, void* stream);
+int rt_launch_order_sort(const uint32_t* d_keys, long long n, uint32_t* d_order, void* d_ws, void* stream);
 // rt_query.hip / rt_query64.hip (+ rt_query64_bvh.hip): n ray queries (include/rt.h rt_scene_cast; rt_query.h), device
 // pointers.  p as a render's (rt_host_render_params, any valid camera) with lds_nodes = 0 and status
 // set; prim_mat: HostScene::prim_mat on the device
@@ -560,6 +567,12 @@ int rt_launch_query(const KernelParams& p, int variant, const rt_ray* rays, rt_h
                     int flags, void* stream);
 int rt_launch_query(const KernelParams64& p, int variant, const rt_ray* rays, rt_hit* hits, const int* prim_mat,
                     long long n, int flags, void* stream);
+// rt_query_ord.hip / rt_query64_ord.hip (+ rt_query64_bvh_ord.hip): the same with lane i on record order[i]
+// (an entry >= n is skipped)
+int rt_launch_query_ordered(const KernelParams& p, int variant, const rt_ray* rays, rt_hit* hits, const int* prim_mat,
+                            long long n, int flags, const uint32_t* order, void* stream);
+int rt_launch_query_ordered(const KernelParams64& p, int variant, const rt_ray* rays, rt_hit* hits, const int* prim_mat,
+                            long long n, int flags, const uint32_t* order, void* stream);
 // rt_list.hip / rt_list64_nl.hip: samples [N_p, N_p + n_samples) of the *n_list listed tile pixels
 // (rt_adaptive.h rt_adaptive_rec; device pointers) added to p.accum / p.nanflag, a zeroed pass
 // workspace whose p.counter[0] is the kernel's zeroed item cursor (rt_list_kernel.h).  p as a
@@ -588,6 +601,18 @@ int rt_launch_radiance(const KernelParams& p, int variant, const rt_path_ray* ra
                        long long n, int n_samples, int chunk, int flags, void* stream);
 int rt_launch_radiance(const KernelParams64& p, int variant, const rt_path_ray* rays, rt_radiance* out,
                        unsigned long long* work, long long n, int n_samples, int chunk, int flags, void* stream);
+// the resolve of rt_launch_radiance alone, and rt_radiance_ord.hip / rt_radiance64_ord_nl.hip: the
+// same query with the items of ray order[i] where ray i's stand (an entry >= n is skipped)
+int rt_launch_radiance_resolve(const KernelParams& p, const rt_path_ray* rays, const unsigned long long* work, rt_radiance* out,
+                               long long n, void* stream);
+int rt_launch_radiance_resolve(const KernelParams64& p, const rt_path_ray* rays, const unsigned long long* work,
+                               rt_radiance* out, long long n, void* stream);
+int rt_launch_radiance_ordered(const KernelParams& p, int variant, const rt_path_ray* rays, rt_radiance* out,
+                               unsigned long long* work, long long n, int n_samples, int chunk, int flags, const uint32_t* order,
+                               void* stream);
+int rt_launch_radiance_ordered(const KernelParams64& p, int variant, const rt_path_ray* rays, rt_radiance* out,
+                               unsigned long long* work, long long n, int n_samples, int chunk, int flags,
+                               const uint32_t* order, void* stream);
 // the render's camera ray of (pixel, sample) for every pixel of p's frame (one shard), row-major
 int rt_launch_camera_rays(const KernelParams& p, int variant, rt_path_ray* rays, int sample, void* stream);
 int rt_launch_camera_rays(const KernelParams64& p, int variant, rt_path_ray* rays, int sample, void* stream);

@@ -14,6 +14,27 @@
 #ifndef RT_QUERY_PART
 #define RT_QUERY_PART 0
 #endif
+// RT_QUERY_ORDERED 1 (rt_query*_ord.hip): the ordered form of the same text under names of its own —
+// lane id traces rays[order[id]] into hits[order[id]] (include/rt.h rt_scene_cast_ordered).  The
+// unordered units' text is unchanged by it.
+#ifndef RT_QUERY_ORDERED
+#define RT_QUERY_ORDERED 0
+#endif
+#if RT_QUERY_ORDERED
+#define RT_QUERY_KERNEL rt_query_ordered_kernel
+#define RT_QUERY_LAUNCH rt_launch_query_ordered
+#define RT_QUERY_BVH_KERNEL rt_query64_bvh_ordered_kernel
+#define RT_QUERY_ORDER_PARAM , const uint32_t* __restrict__ order
+#define RT_QUERY_ORDER_TYPE , const uint32_t*
+#define RT_QUERY_ORDER_ARG , order
+#else
+#define RT_QUERY_KERNEL rt_query_kernel
+#define RT_QUERY_LAUNCH rt_launch_query
+#define RT_QUERY_BVH_KERNEL rt_query64_bvh_kernel
+#define RT_QUERY_ORDER_PARAM
+#define RT_QUERY_ORDER_TYPE
+#define RT_QUERY_ORDER_ARG
+#endif
 
 namespace RT_NS {
 
@@ -26,16 +47,25 @@ __device__ __forceinline__ double q_ints(int lo, int hi) {
   return __builtin_bit_cast(double, (unsigned long long)(unsigned)lo | ((unsigned long long)(unsigned)hi << 32));
 }
 
-// One lane per ray, in the caller's order: lane id traces rays[id] into hits[id].  Rays are neither
-// sorted nor compacted — the caller's coherence is the kernel's.  Block and stack: rt_lane.h.  The
+// One lane per ray, in the caller's order: lane id traces rays[id] into hits[id] — the caller's
+// coherence is the kernel's — or, in the ordered form, rays[order[id]] into hits[order[id]]
+// (rt_order.hip makes such orders).  Nothing is compacted.  Block and stack: rt_lane.h.  The
 // kernel's first argument is its KernelParams, as the render kernels' (rt_trace.h RT_KARGS).
 template <int kVar, bool kInst, int kLeaf>
-__global__ __launch_bounds__(kLaneBlock) void rt_query_kernel(KernelParams P, const rt_ray* __restrict__ rays,
+__global__ __launch_bounds__(kLaneBlock) void RT_QUERY_KERNEL(KernelParams P, const rt_ray* __restrict__ rays,
                                                                rt_hit* __restrict__ hits, const int* __restrict__ prim_mat,
-                                                               long long n, int flags) {
+                                                               long long n, int flags RT_QUERY_ORDER_PARAM) {
   extern __shared__ int smem[];
+#if RT_QUERY_ORDERED
+  // an entry that is no record's index is skipped: nothing is read or written for it
+  const long long slot = (long long)blockIdx.x * kLaneBlock + threadIdx.x;
+  if (slot >= n) return;
+  const long long id = (long long)order[slot];
+  if (id >= n) return;
+#else
   const long long id = (long long)blockIdx.x * kLaneBlock + threadIdx.x;
   if (id >= n) return;
+#endif
   const q16* rp = reinterpret_cast<const q16*>(rays + id);
   const q16 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3], r4 = rp[4];
   const rt_ray q{{r0.x, r0.y, r1.x}, {r1.y, r2.x, r2.y}, r3.x, r3.y, r4.x, 0.0};
@@ -53,7 +83,7 @@ __global__ __launch_bounds__(kLaneBlock) void rt_query_kernel(KernelParams P, co
   if (overflow) atomicOr(P.status, 1);
 }
 
-typedef void (*query_fn)(KernelParams, const rt_ray*, rt_hit*, const int*, long long, int);
+typedef void (*query_fn)(KernelParams, const rt_ray*, rt_hit*, const int*, long long, int RT_QUERY_ORDER_TYPE);
 // the instantiation of a class: rt_kernel_class.h's dispatch, with every field a surface hit does
 // not see (texture level, media mode, material set, workgroup size) at its first value — only
 // var x inst x leaf is instantiated
@@ -67,7 +97,7 @@ static query_fn query_kernel_of_class(KernelClass cls) {
     constexpr KernelClass c{decltype(k)::value...};
     if constexpr (rt_class_compiled(RT_F64, c) && c.tex == 0 && c.media == 0 && !c.mats && !c.narrow &&
                   c.var != RT_VAR_BVH_LOCKSTEP && (c.var == RT_VAR_FLAT) == kFlatPart)
-      return rt_query_kernel<c.var, c.inst, c.leaf>;
+      return RT_QUERY_KERNEL<c.var, c.inst, c.leaf>;
     return nullptr;
   });
 }
@@ -75,21 +105,21 @@ static query_fn query_kernel_of_class(KernelClass cls) {
 }  // namespace RT_NS
 
 #if RT_QUERY_PART == 2
-void* rt_query64_bvh_kernel(KernelClass cls) { return (void*)RT_NS::query_kernel_of_class<false>(cls); }
+void* RT_QUERY_BVH_KERNEL(KernelClass cls) { return (void*)RT_NS::query_kernel_of_class<false>(cls); }
 #else
 #if RT_QUERY_PART == 1
-void* rt_query64_bvh_kernel(KernelClass cls);  // rt_query64_bvh.hip
+void* RT_QUERY_BVH_KERNEL(KernelClass cls);  // rt_query64_bvh.hip (rt_query64_bvh_ord.hip)
 #endif
 
-int rt_launch_query(const KernelParamsT<RT_NS::real>& p, int variant, const rt_ray* rays, rt_hit* hits,
-                    const int* prim_mat, long long n, int flags, void* stream) {
+int RT_QUERY_LAUNCH(const KernelParamsT<RT_NS::real>& p, int variant, const rt_ray* rays, rt_hit* hits,
+                    const int* prim_mat, long long n, int flags RT_QUERY_ORDER_PARAM, void* stream) {
   using namespace RT_NS;
   if (n <= 0) return 0;
   const KernelClass c = rt_class_of(RT_F64, variant);
   query_fn fn = nullptr;
   if (c.var == RT_VAR_FLAT) fn = query_kernel_of_class<true>(c);
 #if RT_QUERY_PART == 1
-  else fn = (query_fn)rt_query64_bvh_kernel(c);
+  else fn = (query_fn)RT_QUERY_BVH_KERNEL(c);
 #else
   else fn = query_kernel_of_class<false>(c);
 #endif
@@ -98,7 +128,7 @@ int rt_launch_query(const KernelParamsT<RT_NS::real>& p, int variant, const rt_r
   if (blocks > 0x7fffffffLL) return -1;
   const size_t lds = lane_stack_bytes(variant, p.stack_depth);
   hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kLaneBlock), lds, (hipStream_t)stream, p, rays, hits, prim_mat, n,
-                     flags);
+                     flags RT_QUERY_ORDER_ARG);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 #endif

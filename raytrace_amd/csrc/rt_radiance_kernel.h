@@ -10,6 +10,25 @@
 #include "rt_trace.h"
 #include "rt_radiance.h"
 
+// RT_RADIANCE_ORDERED 1 (rt_radiance_ord.hip, rt_radiance64_ord_nl.hip): the ordered form of the path
+// kernel and its launcher under names of their own — an item's ray is order[id / n_chunks]
+// (include/rt.h rt_scene_radiance_ordered); the workspace and the result stay indexed by the ray, so
+// the resolve and the camera-ray kernels are the unordered units' alone, whose text is unchanged by it.
+#ifndef RT_RADIANCE_ORDERED
+#define RT_RADIANCE_ORDERED 0
+#endif
+#if RT_RADIANCE_ORDERED
+#define RT_RADIANCE_KERNEL rt_radiance_ordered_kernel
+#define RT_RADIANCE_ORDER_PARAM , const uint32_t* __restrict__ order, uint32_t n_rays
+#define RT_RADIANCE_ORDER_TYPE , const uint32_t*, uint32_t
+#define RT_RADIANCE_LAUNCH rt_launch_radiance_ordered
+#else
+#define RT_RADIANCE_LAUNCH rt_launch_radiance
+#define RT_RADIANCE_KERNEL rt_radiance_kernel
+#define RT_RADIANCE_ORDER_PARAM
+#define RT_RADIANCE_ORDER_TYPE
+#endif
+
 namespace RT_NS {
 
 // the records move as 16-byte vectors: a wave's 64 rays are 4 KB contiguous, its results 2 KB
@@ -37,13 +56,14 @@ __device__ __forceinline__ rt_path_ray load_path_ray(const rt_path_ray* __restri
 // P.counter[0], in the workspace's tail, zeroed by the call — until the ids are exhausted.  A lane
 // sums its chunk in an Acc and adds the nonzero words and the count to the ray's workspace words
 // with 64-bit integer atomics, the flag with atomicOr: the sums do not depend on the chunking or the
-// schedule.  Nothing is sorted or compacted and no single lane is refilled: the wave waits for its
+// schedule.  Nothing is compacted (the ordered form takes the rays in a given order) and no single lane is refilled: the wave waits for its
 // longest lane, as rt_list_kernel's.  Block and stack: rt_lane.h.  The kernel's first argument is
 // its KernelParams (rt_trace.h RT_KARGS).
 template <int kVar, int kTex, int kMedia, bool kMats, bool kInst, int kLeaf>
-__global__ __launch_bounds__(kLaneBlock) void rt_radiance_kernel(KernelParams P, const rt_path_ray* __restrict__ rays,
+__global__ __launch_bounds__(kLaneBlock) void RT_RADIANCE_KERNEL(KernelParams P, const rt_path_ray* __restrict__ rays,
                                                                  unsigned long long* __restrict__ work, long long n_items,
-                                                                 int n_samples, int chunk, int n_chunks, int flags) {
+                                                                 int n_samples, int chunk, int n_chunks,
+                                                                 int flags RT_RADIANCE_ORDER_PARAM) {
   extern __shared__ int smem[];
   const Trav W{smem + threadIdx.x, kLaneBlock, nullptr};
   int overflow = 0;
@@ -55,9 +75,18 @@ __global__ __launch_bounds__(kLaneBlock) void rt_radiance_kernel(KernelParams P,
     // whole wave, the lanes' work below rejoins before the next one
     if (base < 0 || base >= n_items) break;
     const long long id = (long long)base + threadIdx.x;
+#if RT_RADIANCE_ORDERED
+    // an entry that is no ray's index is skipped: nothing is read or written for it
+    const long long slot = id < n_items ? id / n_chunks : 0;
+    const uint32_t ray_of = id < n_items ? order[slot] : n_rays;  // (the launcher bounds the rays below 2^31)
+    if (ray_of < n_rays) {
+      const long long ray = (long long)ray_of;
+      const int k = (int)(id - slot * n_chunks);
+#else
     if (id < n_items) {  // (the last claim may leave lanes idle; the next claim ends the wave)
       const long long ray = id / n_chunks;
       const int k = (int)(id - ray * n_chunks);
+#endif
       const rt_path_ray q = load_path_ray(rays, ray);
       const int k0 = k * chunk, k1 = min(n_samples, (k + 1) * chunk);
       Acc A;
@@ -81,6 +110,7 @@ __global__ __launch_bounds__(kLaneBlock) void rt_radiance_kernel(KernelParams P,
   if (overflow) atomicOr(P.status, 1);
 }
 
+#if !RT_RADIANCE_ORDERED
 // one thread per ray: the workspace's words to the caller's record (rt_radiance.h radiance_resolve)
 __global__ __launch_bounds__(256) void rt_radiance_resolve_kernel(const rt_path_ray* __restrict__ rays,
                                                                   const unsigned long long* __restrict__ work,
@@ -114,7 +144,10 @@ __global__ __launch_bounds__(256) void rt_camera_rays_kernel(KernelParams P, rt_
   rp[3] = r16{q.time, r_ints(q.stream, q.sample0)};
 }
 
-typedef void (*radiance_fn)(KernelParams, const rt_path_ray*, unsigned long long*, long long, int, int, int, int);
+#endif  // !RT_RADIANCE_ORDERED
+
+typedef void (*radiance_fn)(KernelParams, const rt_path_ray*, unsigned long long*, long long, int, int, int,
+                            int RT_RADIANCE_ORDER_TYPE);
 // the instantiation of a variant's class: the render's (var, tex, media, mats, inst, leaf) with the
 // workgroup size's field cleared, as rt_list_kernel.h list_kernel_of; the lockstep BVH base has none
 static radiance_fn radiance_kernel_of(int variant) {
@@ -123,15 +156,19 @@ static radiance_fn radiance_kernel_of(int variant) {
   return rt_with_class(cls, [](auto... k) -> radiance_fn {
     constexpr KernelClass c{decltype(k)::value...};
     if constexpr (rt_class_compiled(RT_F64, c) && !c.narrow && c.var != RT_VAR_BVH_LOCKSTEP)
-      return rt_radiance_kernel<c.var, c.tex, c.media, c.mats, c.inst, c.leaf>;
+      return RT_RADIANCE_KERNEL<c.var, c.tex, c.media, c.mats, c.inst, c.leaf>;
     return nullptr;
   });
 }
 
 }  // namespace RT_NS
 
-int rt_launch_radiance(const KernelParamsT<RT_NS::real>& p, int variant, const rt_path_ray* rays, rt_radiance* out,
-                       unsigned long long* work, long long n, int n_samples, int chunk_arg, int flags, void* stream) {
+int RT_RADIANCE_LAUNCH(const KernelParamsT<RT_NS::real>& p, int variant, const rt_path_ray* rays, rt_radiance* out,
+                       unsigned long long* work, long long n, int n_samples, int chunk_arg, int flags,
+#if RT_RADIANCE_ORDERED
+                       const uint32_t* order,
+#endif
+                       void* stream) {
   using namespace RT_NS;
   if (n <= 0 || n_samples <= 0) return 0;
   if (n * n_samples > (long long)RT_RADIANCE_MAX_IDS) return -1;
@@ -152,10 +189,28 @@ int rt_launch_radiance(const KernelParamsT<RT_NS::real>& p, int variant, const r
   const long long blocks = std::min<long long>((n_items + kLaneBlock - 1) / kLaneBlock, resident / kLaneBlock);
   const size_t lds = lane_stack_bytes(variant, p.stack_depth);
   hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kLaneBlock), lds, (hipStream_t)stream, p, rays, work, n_items, n_samples,
-                     chunk, n_chunks, flags);
+                     chunk, n_chunks, flags
+#if RT_RADIANCE_ORDERED
+                     , order, (uint32_t)n
+#endif
+  );
   if (hipGetLastError() != hipSuccess) return -1;
+#if RT_RADIANCE_ORDERED
+  return rt_launch_radiance_resolve(p, rays, work, out, n, stream);
+}
+#else
   hipLaunchKernelGGL(rt_radiance_resolve_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rays,
                      (const unsigned long long*)work, out, n);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// the resolve alone, for the ordered unit's launcher (p names the precision)
+int rt_launch_radiance_resolve(const KernelParamsT<RT_NS::real>& p, const rt_path_ray* rays, const unsigned long long* work,
+                               rt_radiance* out, long long n, void* stream) {
+  using namespace RT_NS;
+  (void)p;
+  hipLaunchKernelGGL(rt_radiance_resolve_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rays, work,
+                     out, n);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -170,3 +225,4 @@ int rt_launch_camera_rays(const KernelParamsT<RT_NS::real>& p, int variant, rt_p
     hipLaunchKernelGGL(rt_camera_rays_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, rays, sample);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+#endif  // !RT_RADIANCE_ORDERED

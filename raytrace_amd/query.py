@@ -4,7 +4,10 @@ The reference's `Geometry` is a hit function time -> Ray -> (tmin, tmax) -> Mayb
 (Geometry.hs:42); `DeviceScene.cast` evaluates it for n rays at once against the scene's surfaces
 (`constantMedium` volumes are not hit: their events are random draws keyed by pixel and sample).
 Directions may have any non-zero length; `t` is the distance along the normalised direction.  Rays are
-traced in the order given, 64 consecutive rays per wave: coherent neighbours run faster.
+traced in the order given, 64 consecutive rays per wave: coherent neighbours run faster.  For
+incoherent batches (hemisphere probes, secondary rays) `reorder=True` sorts the batch on the device by
+a coherence key first, and `DeviceScene.ray_order` returns that order for reuse (`order=`): the
+results are the unordered call's, bit for bit.
 
     scene = DeviceScene(world)
     h = scene.cast(origins, directions)            # dict of numpy arrays
@@ -57,23 +60,53 @@ def hits_dict(hits: np.ndarray) -> dict:
                 instance=hits["instance"].copy(), material=hits["material"].copy())
 
 
-def cast_records(scene, rays: np.ndarray, precision: str = "f64", any_hit: bool = False, uv: bool = True) -> np.ndarray:
+def order_arg(order, n: int):
+    """A caller's order as the contiguous uint32 array the ordered calls read (kept alive by the caller)."""
+    a = np.ascontiguousarray(order, np.uint32)
+    if a.shape != (n,):
+        raise ValueError(f"order must have shape {(n,)}, not {a.shape}")
+    return a
+
+
+def ray_order_records(scene, rays: np.ndarray) -> np.ndarray:
+    """rt_scene_ray_order on host records (RAY_DTYPE or radiance.PATH_RAY_DTYPE): the batch's coherence
+    order, (n,) uint32 — position i holds the index of the ray to trace i-th."""
+    from .radiance import PATH_RAY_DTYPE
+    if rays.dtype not in (RAY_DTYPE, PATH_RAY_DTYPE):
+        raise ValueError("rays must be RAY_DTYPE or PATH_RAY_DTYPE records")
+    kind = _lib.RT_ORDER_RAYS if rays.dtype == RAY_DTYPE else _lib.RT_ORDER_PATH_RAYS
+    rays = np.ascontiguousarray(rays)
+    order = np.zeros(len(rays), np.uint32)
+    _lib.check(scene._lib.rt_scene_ray_order(scene.handle, rays.ctypes.data_as(ctypes.c_void_p), len(rays), kind,
+                                             order.ctypes.data_as(ctypes.c_void_p)))
+    return order
+
+
+def cast_records(scene, rays: np.ndarray, precision: str = "f64", any_hit: bool = False, uv: bool = True,
+                 reorder: bool = False, order=None) -> np.ndarray:
     """rt_scene_cast on host records: (n,) RAY_DTYPE -> (n,) HIT_DTYPE.  Raises RtError on a
-    traversal-stack overflow (RT_E_STACK)."""
+    traversal-stack overflow (RT_E_STACK).  reorder: trace in the batch's coherence order, computed on
+    the device (rt_scene_cast_ordered); order: in this order (a permutation, e.g. ray_order's)."""
     rays = np.ascontiguousarray(rays, RAY_DTYPE)
     hits = np.zeros(len(rays), HIT_DTYPE)
     ex = _lib.exec_struct(device=scene.device, precision=precision)
+    if reorder or order is not None:
+        o = None if order is None else order_arg(order, len(rays))
+        _lib.check(scene._lib.rt_scene_cast_ordered(scene.handle, ctypes.byref(ex), rays.ctypes.data_as(ctypes.c_void_p),
+                                                    hits.ctypes.data_as(ctypes.c_void_p), len(rays), query_flags(any_hit, uv),
+                                                    None if o is None else o.ctypes.data_as(ctypes.c_void_p)))
+        return hits
     _lib.check(scene._lib.rt_scene_cast(scene.handle, ctypes.byref(ex), rays.ctypes.data_as(ctypes.c_void_p),
                                         hits.ctypes.data_as(ctypes.c_void_p), len(rays), query_flags(any_hit, uv)))
     return hits
 
 
 def cast(world, origins, directions, tmin=1e-4, tmax=np.inf, time=0.0, precision: str = "f64", any_hit: bool = False,
-         uv: bool = True, device: int = 0) -> dict:
+         uv: bool = True, device: int = 0, reorder: bool = False) -> dict:
     """One-shot form: upload `world`, cast, release.  Returns DeviceScene.cast's dict."""
     from .ray import DeviceScene
     scene = DeviceScene(world, device)
     try:
-        return scene.cast(origins, directions, tmin, tmax, time, precision, any_hit, uv)
+        return scene.cast(origins, directions, tmin, tmax, time, precision, any_hit, uv, reorder=reorder)
     finally:
         scene.close()

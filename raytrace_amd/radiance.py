@@ -6,7 +6,9 @@ it for n rays at once — an orthographic or panoramic camera, irradiance probes
 scene's media, materials, background and redirect targets.  Ray i receives samples `sample0 + [0,
 samples)` of Philox stream `stream` (where a render puts the pixel id), so equal records give equal
 results, and `DeviceScene.camera_rays` returns the rays whose radiance is a render's sample word for
-word.  Rays are traced in the order given, 64 consecutive (ray, sample chunk) items per wave.
+word.  Rays are traced in the order given, 64 consecutive (ray, sample chunk) items per wave;
+`reorder=True` / `order=` trace them in a coherence order instead (raytrace_amd.query), with the
+same results and workspace words.
 
     scene = DeviceScene(world)
     rgb, info = scene.radiance(origins, directions, settings, seed, samples=64)
@@ -63,10 +65,11 @@ def make_path_rays(origins, directions, time=0.0, stream=None, sample0=0) -> np.
 
 
 def radiance_records(scene, rays: np.ndarray, settings, seed, samples: int = 1, precision: str = "f64",
-                     unit_dir: bool = False, work: np.ndarray | None = None):
+                     unit_dir: bool = False, work: np.ndarray | None = None, reorder: bool = False, order=None):
     """rt_scene_radiance on host records: (n,) PATH_RAY_DTYPE -> ((n,) RADIANCE_DTYPE, (n, words) uint64
     workspace words).  `work`: the words of an earlier call to add onto (RT_RADIANCE_ACCUMULATE; not
-    modified).  Raises RtError on a traversal-stack overflow (RT_E_STACK)."""
+    modified).  reorder / order: as query.cast_records (rt_scene_radiance_ordered).  Raises RtError on a
+    traversal-stack overflow (RT_E_STACK)."""
     from .ray import _seed64
     rays = np.ascontiguousarray(rays, PATH_RAY_DTYPE)
     n = len(rays)
@@ -77,19 +80,25 @@ def radiance_records(scene, rays: np.ndarray, settings, seed, samples: int = 1, 
     out = np.zeros(n, RADIANCE_DTYPE)
     cs = _lib.camera_struct(settings)
     ex = _lib.exec_struct(device=scene.device, precision=precision)
-    _lib.check(scene._lib.rt_scene_radiance(scene.handle, ctypes.byref(ex), ctypes.byref(cs), _seed64(seed),
-                                            rays.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p),
-                                            w.ctypes.data_as(ctypes.c_void_p), n, int(samples),
-                                            radiance_flags(unit_dir, work is not None)))
+    args = (scene.handle, ctypes.byref(ex), ctypes.byref(cs), _seed64(seed), rays.ctypes.data_as(ctypes.c_void_p),
+            out.ctypes.data_as(ctypes.c_void_p), w.ctypes.data_as(ctypes.c_void_p), n, int(samples),
+            radiance_flags(unit_dir, work is not None))
+    if reorder or order is not None:
+        from .query import order_arg
+        o = None if order is None else order_arg(order, n)
+        _lib.check(scene._lib.rt_scene_radiance_ordered(*args, None if o is None else o.ctypes.data_as(ctypes.c_void_p)))
+    else:
+        _lib.check(scene._lib.rt_scene_radiance(*args))
     return out, w
 
 
 def radiance(world, origins, directions, settings, seed, samples: int = 1, time=0.0, stream=None, sample0=0,
-             precision: str = "f64", unit_dir: bool = False, device: int = 0):
+             precision: str = "f64", unit_dir: bool = False, device: int = 0, reorder: bool = False):
     """One-shot form: upload `world`, query, release.  Returns DeviceScene.radiance's (rgb, info)."""
     from .ray import DeviceScene
     scene = DeviceScene(world, device)
     try:
-        return scene.radiance(origins, directions, settings, seed, samples, time, stream, sample0, precision, unit_dir)
+        return scene.radiance(origins, directions, settings, seed, samples, time, stream, sample0, precision, unit_dir,
+                              reorder=reorder)
     finally:
         scene.close()

@@ -153,21 +153,48 @@ class DeviceScene:
         return self.flat.material_objects
 
     def cast(self, origins, directions, tmin=1e-4, tmax=np.inf, time=0.0, precision: str = "f64",
-             any_hit: bool = False, uv: bool = True) -> dict:
+             any_hit: bool = False, uv: bool = True, reorder: bool = False, order=None) -> dict:
         """Closest hit (or, with any_hit, whether there is one) of n rays against the scene's surfaces
         (rt_scene_cast; raytrace_amd.query).  The arguments broadcast to (n, 3) / (n,); directions
         need not be unit, t is a distance.  Returns numpy arrays: hit (bool), valid, t (inf on a miss),
-        point, normal, front, uv, leaf, instance, material (an index into `materials`)."""
+        point, normal, front, uv, leaf, instance, material (an index into `materials`).  reorder: trace
+        the batch in its coherence order, computed on the device; order: in this order (ray_order's,
+        reused while origins and directions stand) — the results are the same either way."""
         from . import query
         return query.hits_dict(query.cast_records(self, query.make_rays(origins, directions, tmin, tmax, time),
-                                                  precision, any_hit, uv))
+                                                  precision, any_hit, uv, reorder, order))
+
+    def ray_order(self, origins, directions) -> np.ndarray:
+        """The coherence order of n rays (rt_scene_ray_order): (n,) uint32, position i the index of the
+        ray to trace i-th — rays sorted by the cell of their origin in the batch's own box, then by the
+        cell of their direction; for cast / radiance's `order=`."""
+        from . import query
+        return query.ray_order_records(self, query.make_rays(origins, directions))
+
+    def ray_order_async(self, rays_ptr: int, n: int, order_ptr: int, work_ptr: int, stream_ptr: int = 0,
+                        path_rays: bool = False):
+        """Enqueue the order of the n rt_ray (path_rays: rt_path_ray) records at rays_ptr into the n uint32
+        at order_ptr, over a workspace of ray_order_workspace_bytes(n) bytes at work_ptr (device buffers)."""
+        kind = _lib.RT_ORDER_PATH_RAYS if path_rays else _lib.RT_ORDER_RAYS
+        _lib.check(self._lib.rt_scene_ray_order_async(self.handle, ctypes.c_void_p(rays_ptr), int(n), kind,
+                                                      ctypes.c_void_p(order_ptr), ctypes.c_void_p(work_ptr),
+                                                      ctypes.c_void_p(stream_ptr or None)))
+
+    def ray_order_workspace_bytes(self, n: int) -> int:
+        return int(self._lib.rt_ray_order_workspace_bytes(int(n)))
 
     def cast_async(self, rays_ptr: int, hits_ptr: int, n: int, stream_ptr: int = 0, precision: str = "f64",
-                   any_hit: bool = False, uv: bool = True):
+                   any_hit: bool = False, uv: bool = True, order_ptr: int = 0):
         """Enqueue n queries from the device buffer of rt_ray records at rays_ptr (query.RAY_DTYPE) into
-        the rt_hit records at hits_ptr (query.HIT_DTYPE), e.g. torch uint8 tensors' data_ptr()."""
+        the rt_hit records at hits_ptr (query.HIT_DTYPE), e.g. torch uint8 tensors' data_ptr().
+        order_ptr: n uint32 on the device, the order to trace in (rt_scene_cast_ordered_async)."""
         from . import query
         ex = _lib.exec_struct(device=self.device, precision=precision)
+        if order_ptr:
+            _lib.check(self._lib.rt_scene_cast_ordered_async(self.handle, ctypes.byref(ex), ctypes.c_void_p(rays_ptr),
+                                                             ctypes.c_void_p(hits_ptr), int(n), query.query_flags(any_hit, uv),
+                                                             ctypes.c_void_p(order_ptr), ctypes.c_void_p(stream_ptr or None)))
+            return
         _lib.check(self._lib.rt_scene_cast_async(self.handle, ctypes.byref(ex), ctypes.c_void_p(rays_ptr),
                                                  ctypes.c_void_p(hits_ptr), int(n), query.query_flags(any_hit, uv),
                                                  ctypes.c_void_p(stream_ptr or None)))
@@ -180,27 +207,36 @@ class DeviceScene:
         return bool(w.value)
 
     def radiance(self, origins, directions, settings: CameraSettings, seed, samples: int = 1, time=0.0, stream=None,
-                 sample0=0, precision: str = "f64", unit_dir: bool = False):
+                 sample0=0, precision: str = "f64", unit_dir: bool = False, reorder: bool = False, order=None):
         """The path tracer on n rays of the caller (rt_scene_radiance; raytrace_amd.radiance): each ray
         receives samples sample0 + [0, samples) of Philox stream `stream` (default: the ray's index) and
         returns their mean.  Of `settings` only cs_maxRecursionDepth, the background and the redirect
         targets are read.  Returns (rgb (n, 3) float64, info) with info = dict(status (1 ok, -1 malformed
-        ray, 2 NaN-flagged), samples, work: the (n, words) uint64 workspace words)."""
+        ray, 2 NaN-flagged), samples, work: the (n, words) uint64 workspace words).  reorder / order: as
+        cast's; a refinement loop that only advances sample0 reuses one order."""
         from . import radiance as rad
         rays = rad.make_path_rays(origins, directions, time, stream, sample0)
-        out, work = rad.radiance_records(self, rays, settings, seed, samples, precision, unit_dir)
+        out, work = rad.radiance_records(self, rays, settings, seed, samples, precision, unit_dir, reorder=reorder,
+                                         order=order)
         return out["rgb"].copy(), dict(status=out["status"].copy(), samples=out["samples"].copy(), work=work)
 
     def radiance_async(self, rays_ptr: int, out_ptr: int, work_ptr: int, n: int, samples: int, settings: CameraSettings,
                        seed, stream_ptr: int = 0, accumulate: bool = False, unit_dir: bool = False,
-                       precision: str = "f64"):
+                       precision: str = "f64", order_ptr: int = 0):
         """Enqueue `samples` samples of each of the n rt_path_ray records at rays_ptr (radiance.PATH_RAY_DTYPE)
         into the rt_radiance records at out_ptr (radiance.RADIANCE_DTYPE), over the caller's workspace at
         work_ptr (radiance.workspace_bytes(n, precision) bytes, 16-byte aligned) — device buffers, e.g.
-        torch uint8 tensors' data_ptr().  accumulate: add onto the workspace instead of zeroing it."""
+        torch uint8 tensors' data_ptr().  accumulate: add onto the workspace instead of zeroing it.
+        order_ptr: n uint32 on the device, the order to take the rays in (rt_scene_radiance_ordered_async)."""
         from . import radiance as rad
         cs = _lib.camera_struct(settings)
         ex = _lib.exec_struct(device=self.device, precision=precision)
+        if order_ptr:
+            _lib.check(self._lib.rt_scene_radiance_ordered_async(
+                self.handle, ctypes.byref(ex), ctypes.byref(cs), _seed64(seed), ctypes.c_void_p(rays_ptr),
+                ctypes.c_void_p(out_ptr), ctypes.c_void_p(work_ptr), int(n), int(samples),
+                rad.radiance_flags(unit_dir, accumulate), ctypes.c_void_p(order_ptr), ctypes.c_void_p(stream_ptr or None)))
+            return
         _lib.check(self._lib.rt_scene_radiance_async(self.handle, ctypes.byref(ex), ctypes.byref(cs), _seed64(seed),
                                                      ctypes.c_void_p(rays_ptr), ctypes.c_void_p(out_ptr),
                                                      ctypes.c_void_p(work_ptr), int(n), int(samples),
