@@ -1,6 +1,6 @@
 // rt_adaptive.h — adaptive film passes: per-pixel arithmetic (host and device, as rt_film.h's, so a
 // CPU program calls exactly what the kernels run) and the launchers of rt_adaptive.hip.  Not part of
-// the public ABI (include/rt.h rt_adaptive_*; rt_api.hip holds the state and the entry points).
+// the public ABI (include/rt.h rt_adaptive_*; rt_api_film.hip holds the state and the entry points).
 //
 // A film becomes NON-UNIFORM at its first adaptive pass: it gains a count plane, two uint32 per tile
 // pixel, the pixel's samples N_p and passes K_p (a shard's padding rows hold (0, 0)).  A pass of n

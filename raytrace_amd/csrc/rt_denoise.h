@@ -1,6 +1,6 @@
 // rt_denoise.h — the film's variance-guided denoiser: per-pixel arithmetic (host and device, so a
 // CPU program can call exactly what the kernels of rt_denoise.hip run) and the launchers.  Not part
-// of the public ABI (include/rt.h rt_denoise_*; rt_api.hip holds the buffers and the entry points).
+// of the public ABI (include/rt.h rt_denoise_*; rt_api_film.hip holds the buffers and the entry points).
 //
 // An edge-stopping a-trous wavelet filter (5 x 5 B3-spline taps at step 2^i per level) of the film's
 // mean colour demodulated by the first-hit albedo, guided by the first-hit normal and depth

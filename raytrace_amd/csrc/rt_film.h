@@ -1,6 +1,6 @@
 // rt_film.h — the progressive film: per-pixel arithmetic (host and device, so a CPU program can
 // call exactly what the kernels run) and the launchers of rt_film.hip.  Not part of the public
-// ABI (include/rt.h rt_film_*; rt_api.hip holds the film's state and entry points).
+// ABI (include/rt.h rt_film_*; rt_api_film.hip holds the film's state and entry points).
 //
 // A film keeps, per tile pixel, the TOTAL fixed-point sums of every sample added so far (the
 // render workspace's layout: RT_ACC_WORDS int64 words, rt_internal.h), the NaN flag and one

@@ -1,5 +1,5 @@
 // rt_internal.h — device-side layout shared by the host scene builder (rt_build.cpp), the
-// C-ABI (rt_api.hip) and the render kernel (rt_kernel.hip / rt_trace.h).  Not part of the
+// C-ABI (rt_api*.hip) and the render kernel (rt_kernel.hip / rt_trace.h).  Not part of the
 // public ABI (include/rt.h).  Plain C++ (no HIP types) so the builder compiles anywhere.
 //
 // HBM layout (16-B records, read with one dwordx4 load per lane):
@@ -478,7 +478,7 @@ inline int rt_host_stack_depth(const HostScene& H) { return H.max_depth > 1 ? H.
 template <class R>
 int rt_host_make_params(const rt_camera_settings* cs, uint64_t seed, const rt_exec* ex, KernelParamsT<R>& P,
                         std::string& err);
-// The record pointers of one precision, in host memory (rt_host_records) or in a device's (rt_api.hip
+// The record pointers of one precision, in host memory (rt_host_records) or in a device's (rt_api_internal.h
 // DevArrays): the fill below copies them and never reads through them
 template <class R>
 struct SceneRecordsT {

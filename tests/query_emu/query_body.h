@@ -3,7 +3,7 @@
 
 // every ray through the instantiation the device's dispatch picks (rt_query_kernel.h
 // query_kernel_of_class: the variant's class with tex, media, mats and narrow cleared), its
-// arguments made as rt_api.hip cast_enqueue makes them
+// arguments made as rt_api_query.hip cast_enqueue makes them (unit_camera, one_shard)
 int cast(const HostScene& H, const rt_ray* rays, rt_hit* hits, long long n, int flags, std::string& err) {
   using namespace RT_NS;
   rt_camera_settings cs{};
@@ -21,7 +21,7 @@ int cast(const HostScene& H, const rt_ray* rays, rt_hit* hits, long long n, int 
   L.resident_lanes = 4096;
   RT_NS::KernelParams P;
   if (int rc = rt_host_render_params(H, variant, rt_host_records<real>(H), &cs, 0, &ex, L, P, err)) return rc;
-  // (tests: fewer stack rows than the scene's BVH needs, as rt_api.hip cast_enqueue reads the knob)
+  // (tests: fewer stack rows than the scene's BVH needs, as rt_api_query.hip cast_enqueue reads the knob)
   if (const char* e = rt_knob("RT_AMD_CAST_STACK")) P.stack_depth = std::max(1, std::min(P.stack_depth, atoi(e)));
   std::vector<int> stack(P.stack_depth + 1);
   const Trav W{stack.data(), 1, nullptr};

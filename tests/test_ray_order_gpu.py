@@ -341,3 +341,31 @@ def test_python_surface(gpu, precision):
         sc.cast(o, d, precision=precision, order=np.zeros(1000, np.uint32))
     with pytest.raises(R.RtInvalid):
         rs.radiance(ro, rd, cs, seed, precision=precision, order=np.full(len(ro), len(ro), np.uint32))
+
+
+# ---- 10. a synchronous ordered query that accumulates onto a host workspace
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_sync_ordered_radiance_accumulates_onto_a_host_workspace(gpu, precision):
+    """rt_scene_radiance_ordered with RT_RADIANCE_ACCUMULATE and a host workspace: the call uploads
+    the caller's words, adds onto them in the order's sequence and returns them.  Two calls of 2
+    samples (the second with sample0 advanced by 2, over the first one's words), plain, with an order
+    computed on the device and with a host order (the reversed permutation), give one another's records
+    and workspace words bit for bit, and those of one plain call of 4 samples.  130 rays: two full waves
+    and two lanes."""
+    cs, _, seed = scene("cornell")
+    sc = radiance_scene("cornell")
+    n = 130
+    rays = sc.camera_rays(cs, seed, 0, precision)
+    rays = rays[np.random.default_rng(5).permutation(len(rays))[:n]].copy()
+    later = rays.copy()
+    later["sample0"] += 2
+
+    def records(recs, samples, **kw):
+        return rad.radiance_records(sc, recs, cs, seed, samples, precision, unit_dir=True, **kw)
+
+    want_out, want_work = records(rays, 4)
+    assert (want_out["samples"] == 4).all() and want_out["rgb"].max() > 0
+    for kw in (dict(), dict(reorder=True), dict(order=np.arange(n - 1, -1, -1, dtype=np.uint32))):
+        _, first = records(rays, 2, **kw)
+        out, work = records(later, 2, work=first, **kw)
+        assert out.tobytes() == want_out.tobytes() and work.tobytes() == want_work.tobytes(), kw
