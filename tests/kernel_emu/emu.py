@@ -89,6 +89,35 @@ def scene_info(world):
     return dict(zip(["n_nodes", "surface_nodes", "max_depth", "n_prims", "flat", "boxes", "prefix", "leaf_kind"], info.tolist()))
 
 
+def scene_variant(world):
+    """The variant code (rt_internal.h RT_VAR_*) the host build gives `world`: rt_host_variant(H)."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from raytrace_amd import _lib as R
+    from raytrace_amd.scene import FlatScene, flatten
+    flat = world if isinstance(world, FlatScene) else flatten(world)
+    sc = R.scene_struct(flat)
+    v = ctypes.c_int(-1)
+    rc = lib().rt_emu_scene_variant(ctypes.byref(sc), ctypes.byref(v))
+    if rc != 0:
+        raise RuntimeError(f"rt_emu_scene_variant failed {rc}: {lib().rt_emu_last_error().decode()}")
+    return v.value
+
+
+def variant_of(flat, n_media, noise, mats, tex, inst, leaf_kind, media_late, stack_depth):
+    """The scalar rt_host_variant(...) of rt_build.cpp, passed through."""
+    return int(lib().rt_emu_variant_of(*(ctypes.c_int(int(x)) for x in (flat, n_media, noise, mats, tex, inst, leaf_kind,
+                                                                         media_late, stack_depth))))
+
+
+def class_of(precision, variant):
+    """rt_class_of(f64, variant) of rt_kernel_class.h: ((var, tex, media, mats, inst, leaf, narrow),
+    rt_class_block, rt_class_compiled)."""
+    out = (ctypes.c_int * 9)()
+    lib().rt_emu_class_of(ctypes.c_int(precision == "f64"), ctypes.c_int(variant), out)
+    return tuple(out[:7]), out[7], bool(out[8])
+
+
 _ARRAYS = ["prims", "prim_uv", "flat_recs", "motions", "uvframes", "texels", "perlin_grad", "prim_shade", "mats",
            "texs", "boxes", "instances", "media"]
 # the items of rt_emu_scene_digest, in its order (rt_emu.cpp)

@@ -145,6 +145,33 @@ int rt_emu_scene_info(const rt_scene* sc, int* info) {
 }
 }
 
+// Which kernel class a scene gets (test tooling, tests/class_scenes.py): the product's own
+// rt_host_variant and rt_class_of, passed through.
+extern "C" {
+// the variant code the host gives this scene (rt_host_variant(H)) in *variant
+int rt_emu_scene_variant(const rt_scene* sc, int* variant) {
+  HostScene H;
+  int rc = rt_host_build_scene(sc, H, g_err);
+  if (rc) return rc;
+  *variant = rt_host_variant(H);
+  return RT_OK;
+}
+// the variant code of a scene's properties one by one (the scalar rt_host_variant)
+int rt_emu_variant_of(int flat, int n_media, int noise, int mats, int tex, int inst, int leaf_kind, int media_late,
+                      int stack_depth) {
+  return rt_host_variant(flat != 0, n_media, noise != 0, mats != 0, tex != 0, inst != 0, leaf_kind, media_late != 0,
+                         stack_depth);
+}
+// rt_class_of(f64, variant) as out[0..6] = var, tex, media, mats, inst, leaf, narrow; out[7] = rt_class_block,
+// out[8] = rt_class_compiled of that class
+void rt_emu_class_of(int f64, int variant, int* out) {
+  const KernelClass c = rt_class_of(f64 != 0, variant);
+  const int f[9] = {c.var, c.tex, c.media, c.mats, c.inst, c.leaf, c.narrow, rt_class_block(f64 != 0, c),
+                    rt_class_compiled(f64 != 0, c)};
+  for (int k = 0; k < 9; ++k) out[k] = f[k];
+}
+}
+
 // The kernel arguments of a render (test tooling, tests/test_render_params.py): every member of
 // KernelParams (../target_defer/kp_members.h) by name with its values as doubles (exact for every
 // int, uint32, float and double), records field by field (no padding), pointers as null (0) or not (1).
